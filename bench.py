@@ -7,6 +7,22 @@ random-init weights (no network => no real dataset), bf16 autocast
 compute, full training step in the timed region (forward 8 iters +
 sequence loss + backward + gradient all-reduce + Adam step).
 
+A plain run sets up, warms up, times --steps steps and prints one JSON
+result line; --dump-outputs DIR also writes what the last timed step
+returned (loss.npy, final_flow.npy; float32) so two builds can be compared
+output for output.  --full is where measurements beyond the headline
+figure go; this benchmark has none, so it changes nothing today.
+
+Reproducibility: weights, batch and point order are seeded.  The GPU
+kernels reduce through fp32 atomics, so two runs of one forward already
+differ at rounding level (about one bf16 ulp per flow component under
+autocast).  Adam turns such noise into full-size steps wherever a gradient
+is noise-dominated, and at lr=1e-3 two runs drift ~10% apart in 20 steps.
+The learning rate therefore defaults to 0: every kernel of the step still
+runs (the step time is the same, measured), the weights keep their seeded
+values and every timed step computes the same function, so run-to-run
+differences stay at that rounding level.  --lr 1e-3 restores real updates.
+
 Single node, one rank per GPU over RCCL:
   python bench.py --gpus 1 --steps 16 --warmup 4
   python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 \
@@ -26,9 +42,11 @@ import os
 import sys
 import time
 
+import numpy as np
 import torch
 
 BASELINE_PAIRS_PER_S = 1.85
+DUMP_BYTES_MAX = 64 << 20  # --dump-outputs budget over all arrays
 
 
 def parse_args():
@@ -49,10 +67,34 @@ def parse_args():
     p.add_argument("--refine", action="store_true",
                    help="stage-2 benchmark: frozen backbone + refine head, "
                         "32 GRU iterations (BASELINE config 4)")
+    p.add_argument("--lr", type=float, default=0.0,
+                   help="Adam learning rate (default 0: the full optimizer step "
+                        "runs but the weights stay put, see the module docstring)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write the last step's outputs "
+                        "(loss, final flow) as DIR/<name>.npy")
+    p.add_argument("--full", action="store_true",
+                   help="also run the measurements beyond the headline figure "
+                        "(none in this benchmark: same as a plain run)")
     args = p.parse_args()
     if args.refine and args.iters == 8:
         args.iters = 32  # reference run.sh stage-2 convention
     return args
+
+
+def dump_outputs(out_dir, arrays):
+    """Write {name: tensor} as out_dir/<name>.npy (float32).  An array over
+    its share of DUMP_BYTES_MAX is cut to a fixed seeded sample of its
+    flattened elements (same indices every run)."""
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BYTES_MAX // len(arrays)
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.nbytes > share:
+            keep = np.random.default_rng(0).choice(
+                a.size, share // a.itemsize, replace=False)
+            a = a.reshape(-1)[np.sort(keep)]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def main():
@@ -81,6 +123,9 @@ def main():
     amp = args.amp and cuda
 
     torch.manual_seed(1234 + info.rank)
+    # the datasets subsample points through numpy's global RNG: seed it so
+    # the batch (point order included) is the same on every run
+    np.random.seed(1234 + info.rank)
     if args.refine:
         model = PVRaftRefine(truncate_k=args.truncate_k).to(device)
         model.freeze_backbone()
@@ -91,7 +136,7 @@ def main():
     broadcast_module(model)
     reducer = GradReducer(model)
     optimizer = torch.optim.Adam(
-        [p for p in model.parameters() if p.requires_grad], lr=1e-3)
+        [p for p in model.parameters() if p.requires_grad], lr=args.lr)
     batch = synthetic_batch(args.batch, args.points, device=device, seed=100 + info.rank)
 
     model.train()
@@ -115,7 +160,7 @@ def main():
             loss = graphed.replay()
             reducer.reduce_all()
             optimizer.step()
-            return loss
+            return loss, graphed.static_final_flow
 
     else:
 
@@ -128,7 +173,8 @@ def main():
             loss.backward()
             reducer.finalize()
             optimizer.step()
-            return loss
+            final = est_flow[-1] if isinstance(est_flow, (list, tuple)) else est_flow
+            return loss, final
 
     for _ in range(args.warmup):
         step()
@@ -138,8 +184,9 @@ def main():
     if cuda:
         torch.cuda.synchronize()
     t0 = time.perf_counter()
+    out = None
     for _ in range(args.steps):
-        step()
+        out = step()
     if cuda:
         torch.cuda.synchronize()
     if info.distributed:
@@ -151,6 +198,9 @@ def main():
     if info.distributed:
         torch.distributed.all_reduce(el, op=torch.distributed.ReduceOp.MAX)
     elapsed = el.item()
+
+    if args.dump_outputs and info.is_main and out is not None:
+        dump_outputs(args.dump_outputs, {"loss": out[0], "final_flow": out[1]})
 
     n_gpus = info.world_size if cuda else args.gpus
     global_batch = args.batch * info.world_size
@@ -182,6 +232,7 @@ def main():
                         "truncate_k": args.truncate_k,
                         "parallelism": f"dp{info.world_size}",
                         "hipgraph": use_graph,
+                        "lr": args.lr,
                     },
                 }
             )

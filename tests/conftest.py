@@ -1,8 +1,16 @@
+import os
 import random
+import sys
 
 import numpy as np
 import pytest
 import torch
+
+# the package is built and imported in-tree (never installed): make the
+# checkout root importable whichever way pytest is started
+_REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if _REPO not in sys.path:
+    sys.path.insert(0, _REPO)
 
 
 def pytest_configure(config):

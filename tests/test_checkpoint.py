@@ -76,26 +76,18 @@ def test_train_state_roundtrip(tmp_path):
 def test_state_dict_parity_with_reference_model(refine):
     """Key-for-key, shape-for-shape state-dict parity with the ACTUAL
     reference model classes (checkpoints interchangeable both ways).
-    Runs only where the reference repo is mounted (read-only import)."""
-    import argparse
-    import importlib
-    import sys
+    The reference side is the recorded state_dict() key -> shape table of
+    RSF / RSF_refine built with corr_levels=3, base_scales=0.25,
+    truncate_k=64 (tests/golden/reference_state_dict_shapes.json)."""
+    import json
 
-    if not os.path.isdir("/root/reference/model"):
-        pytest.skip("reference repo not available")
-    sys.path.insert(0, "/root/reference")
-    try:
-        try:
-            mod = importlib.import_module(
-                "model.RAFTSceneFlowRefine" if refine else "model.RAFTSceneFlow"
-            )
-        except ImportError as e:  # missing reference-era deps (torch_scatter)
-            pytest.skip(f"reference model unimportable: {e}")
-        cls = getattr(mod, "RSF_refine" if refine else "RSF")
-        args = argparse.Namespace(corr_levels=3, base_scales=0.25, truncate_k=64)
-        ref_sd = {k: tuple(v.shape) for k, v in cls(args).state_dict().items()}
-    finally:
-        sys.path.remove("/root/reference")
+    golden = os.path.join(
+        os.path.dirname(os.path.abspath(__file__)), "golden",
+        "reference_state_dict_shapes.json")
+    with open(golden) as f:
+        recorded = json.load(f)["RSF_refine" if refine else "RSF"]
+    ref_sd = {k: tuple(v) for k, v in recorded.items()}
+    assert len(ref_sd) == (124 if refine else 95)
 
     from pvraft_amd.model import PVRaft, PVRaftRefine
 
