@@ -4,6 +4,9 @@
 #include <hip/hip_runtime.h>
 
 void launch_knn_graph(const float*, int*, int, int, int, hipStream_t);
+void launch_knn_interp(const float*, const float*, const float*, float*, int*,
+                       float*, int, int, int, int, int, float, hipStream_t);
+int knn_interp_tile_pts();
 void launch_morton_keys(const float*, const float*, const float*, long*,
                         int, long, hipStream_t);
 void launch_gather_edge_fwd(const void*, const int*, const float*, void*,
@@ -174,6 +177,41 @@ torch::Tensor knn_graph(torch::Tensor xyz, int64_t k) {
   launch_knn_graph(xyz.data_ptr<float>(), out.data_ptr<int>(), B, N, (int)k,
                    stream());
   return out;
+}
+
+// support (B,N,3), values (B,N,C), query (B,M,3), all fp32 contiguous ->
+// {out (B,M,C) f32, idx (B,M,min(k,N)) i32, w (B,M,min(k,N)) f32}
+std::vector<torch::Tensor> knn_interp_fwd(torch::Tensor support,
+                                          torch::Tensor values,
+                                          torch::Tensor query, int64_t k,
+                                          double eps) {
+  check_f32(support, "support_xyz");
+  check_f32(values, "values");
+  check_f32(query, "query_xyz");
+  TORCH_CHECK(support.dim() == 3 && support.size(2) == 3, "support_xyz must be (B,N,3)");
+  TORCH_CHECK(query.dim() == 3 && query.size(2) == 3, "query_xyz must be (B,M,3)");
+  TORCH_CHECK(values.dim() == 3, "values must be (B,N,C)");
+  TORCH_CHECK(values.device() == support.device() && query.device() == support.device(),
+              "knn_interp inputs must share a device");
+  const int64_t B = support.size(0), N = support.size(1);
+  const int64_t M = query.size(1), C = values.size(2);
+  TORCH_CHECK(query.size(0) == B && values.size(0) == B && values.size(1) == N,
+              "knn_interp batch / support size mismatch");
+  TORCH_CHECK(k >= 1 && k <= 16, "knn_interp requires 1 <= k <= 16");
+  TORCH_CHECK(B >= 1 && B <= 65535 && N >= 1 && M >= 1 && C >= 1,
+              "knn_interp requires 1 <= B <= 65535, N, M, C >= 1");
+  TORCH_CHECK(N < (1L << 31) / 4 && M < (1L << 31) - 256 && C < (1L << 31),
+              "knn_interp sizes exceed 32-bit point indexing");
+  TORCH_CHECK(eps >= 0.0, "knn_interp requires eps >= 0");
+  const int keff = (int)std::min<int64_t>(k, N);
+  auto out = torch::empty({B, M, C}, values.options());
+  auto idx = torch::empty({B, M, keff}, values.options().dtype(torch::kInt32));
+  auto w = torch::empty({B, M, keff}, values.options());
+  launch_knn_interp(support.data_ptr<float>(), values.data_ptr<float>(),
+                    query.data_ptr<float>(), out.data_ptr<float>(),
+                    idx.data_ptr<int>(), w.data_ptr<float>(), (int)B, (int)N,
+                    (int)M, (int)C, keff, (float)eps, stream());
+  return {out, idx, w};
 }
 
 torch::Tensor gather_edge_concat_fwd(torch::Tensor feats, torch::Tensor idx,
@@ -1159,6 +1197,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("knn_gnmp_fwd", &knn_gnmp_fwd);
   m.def("knn_gnmp_bwd", &knn_gnmp_bwd);
   m.def("knn_graph", &knn_graph, "fused kNN graph (CDNA4)");
+  m.def("knn_interp_fwd", &knn_interp_fwd);
+  m.attr("KNN_INTERP_TILE") = knn_interp_tile_pts();
   m.def("gather_edge_concat_fwd", &gather_edge_concat_fwd);
   m.def("gather_edge_concat_bwd", &gather_edge_concat_bwd);
   m.def("gather_edge_bwd_csr", &gather_edge_bwd_csr);

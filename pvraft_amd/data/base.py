@@ -16,6 +16,11 @@ from torch.utils.data import Dataset
 
 
 class SceneFlowDataset(Dataset):
+    # opt-in: items also carry "full": [pc1_full (1,n,3), mask_full (1,n,1),
+    # flow_full (1,n,3)], the first cloud and its ground truth BEFORE
+    # subsampling (dense-flow evaluation)
+    return_full = False
+
     def __init__(self, nb_points: int):
         super().__init__()
         self.nb_points = nb_points
@@ -32,9 +37,18 @@ class SceneFlowDataset(Dataset):
         )
 
     def _load_item(self, idx: int):
-        sequence, ground_truth = self.subsample_points(*self.load_sequence(idx))
+        sequence, ground_truth = self.load_sequence(idx)
+        full = None
+        if self.return_full:
+            # references to the pre-subsample arrays (subsample_points
+            # rebinds, never mutates); no extra RNG draw
+            full = [sequence[0], ground_truth[0], ground_truth[1]]
+        sequence, ground_truth = self.subsample_points(sequence, ground_truth)
         sequence, ground_truth = self.to_torch(sequence, ground_truth)
-        return {"sequence": sequence, "ground_truth": ground_truth}
+        data = {"sequence": sequence, "ground_truth": ground_truth}
+        if full is not None:
+            data["full"] = self.to_torch(full, [])[0]
+        return data
 
     @staticmethod
     def to_torch(sequence, ground_truth):

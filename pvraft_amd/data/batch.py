@@ -22,6 +22,13 @@ class Batch:
             self.data[key] = [
                 torch.cat([s[key][i] for s in samples], dim=0) for i in range(2)
             ]
+        if any("full" in s for s in samples):
+            # full-resolution clouds have ragged lengths: no batching
+            if len(samples) != 1:
+                raise ValueError(
+                    f'"full" clouds are ragged and cannot be batched: got {len(samples)} samples, need 1'
+                )
+            self.data["full"] = list(samples[0]["full"])
 
     def __getitem__(self, key: str):
         return self.data[key]

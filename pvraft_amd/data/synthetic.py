@@ -16,18 +16,22 @@ from .batch import Batch
 
 
 class SyntheticSceneFlow(SceneFlowDataset):
-    def __init__(self, nb_points: int, length: int = 256, seed: int = 0, extent: float = 10.0):
+    def __init__(self, nb_points: int, length: int = 256, seed: int = 0, extent: float = 10.0,
+                 full_points=None):
         super().__init__(nb_points)
         self.length = length
         self.seed = seed
         self.extent = extent
+        # clouds are generated with full_points points (>= nb_points) and
+        # subsampled to nb_points; None keeps the historical stream
+        self.full_points = full_points
 
     def __len__(self):
         return self.length
 
     def load_sequence(self, idx: int):
         rng = np.random.default_rng(self.seed * 1_000_003 + idx)
-        n = self.nb_points
+        n = self.nb_points if self.full_points is None else self.full_points
         pc1 = (rng.random((n, 3), dtype=np.float32) - 0.5) * self.extent
         # smooth flow: global translation + small rotation + noise
         t = rng.normal(0.0, 0.5, size=(1, 3)).astype(np.float32)

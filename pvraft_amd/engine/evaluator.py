@@ -8,6 +8,12 @@ On GPU the forward is served by the hipGraph Predictor (fixed shapes); it
 exposes every per-iteration flow, so the logged loss is the same
 gamma-weighted sequence loss the reference's test.py computes
 (test.py:122).  Disable with --no_hipgraph for the eager path.
+
+--dense (absent in the reference, whose evaluation is subset-only) also
+interpolates the final flow from the sampled pc1 onto the full-resolution
+cloud (ops.knn_interpolate, --dense_k neighbours) and reports dense_*
+metrics over every masked point; the sparse path and its metrics are
+untouched.
 """
 
 from __future__ import annotations
@@ -38,7 +44,9 @@ def build_eval_dataset(args):
         ddir = os.path.join(args.root, "data", "kitti_processed")
         return Kitti(ddir, args.max_points)
     if args.dataset == "SYNTH":
-        return SyntheticSceneFlow(args.max_points, length=getattr(args, "synth_len", 32), seed=7)
+        full = 4 * args.max_points if getattr(args, "dense", False) else None
+        return SyntheticSceneFlow(args.max_points, length=getattr(args, "synth_len", 32), seed=7,
+                                  full_points=full)
     raise ValueError(f"Unknown dataset {args.dataset!r}")
 
 
@@ -48,6 +56,12 @@ def evaluate(args):
     device = torch.device("cuda:0") if torch.cuda.is_available() else torch.device("cpu")
 
     dataset = build_eval_dataset(args)
+    dense = bool(getattr(args, "dense", False))
+    dense_k = int(getattr(args, "dense_k", 3))
+    if dense:
+        from pvraft_amd import ops
+
+        dataset.return_full = True
     loader = DataLoader(
         dataset,
         batch_size=1,
@@ -75,6 +89,7 @@ def evaluate(args):
         predictor = Predictor(model, points=args.max_points, batch=1, iters=TEST_ITERS,
                               amp=bool(getattr(args, "amp", False)))
     sums = [0.0] * 5
+    dense_sums = [0.0] * 4
     n = 0
     for batch in loader:
         batch = batch.to(device, non_blocking=True)
@@ -98,6 +113,14 @@ def evaluate(args):
         epe3d, accs, accr, outl = compute_epe(final.float(), batch)
         for j, v in enumerate((loss.item(), epe3d, accs, accr, outl)):
             sums[j] += v
+        if dense:
+            pc1_full, mask_full, flow_full = batch["full"]
+            flow_dense, _, _ = ops.knn_interpolate(
+                batch["sequence"][0], final.float(), pc1_full, dense_k
+            )
+            dense_m = compute_epe(flow_dense, {"ground_truth": [mask_full, flow_full]})
+            for j, v in enumerate(dense_m):
+                dense_sums[j] += v
         if dump:
             import numpy as np
 
@@ -106,16 +129,32 @@ def evaluate(args):
             np.save(os.path.join(d, "pc1.npy"), batch["sequence"][0].cpu().numpy())
             np.save(os.path.join(d, "pc2.npy"), batch["sequence"][1].cpu().numpy())
             np.save(os.path.join(d, "flow.npy"), final.cpu().numpy())
+            if dense:
+                np.save(os.path.join(d, "pc1_full.npy"), pc1_full.cpu().numpy())
+                np.save(os.path.join(d, "flow_dense.npy"), flow_dense.cpu().numpy())
         n += 1
     means = [s / max(n, 1) for s in sums]
     log.info(
         f"[test {args.dataset}] loss={means[0]:.4f} EPE3D={means[1]:.4f} "
         f"Acc3DS={means[2]:.4f} Acc3DR={means[3]:.4f} Outlier={means[4]:.4f}"
     )
-    return {
+    results = {
         "loss": means[0],
         "epe": means[1],
         "acc3d_strict": means[2],
         "acc3d_relax": means[3],
         "outlier": means[4],
     }
+    if dense:
+        dmeans = [s / max(n, 1) for s in dense_sums]
+        log.info(
+            f"[test {args.dataset} dense k={dense_k}] EPE3D={dmeans[0]:.4f} "
+            f"Acc3DS={dmeans[1]:.4f} Acc3DR={dmeans[2]:.4f} Outlier={dmeans[3]:.4f}"
+        )
+        results.update(
+            dense_epe=dmeans[0],
+            dense_acc3d_strict=dmeans[1],
+            dense_acc3d_relax=dmeans[2],
+            dense_outlier=dmeans[3],
+        )
+    return results

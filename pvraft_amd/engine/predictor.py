@@ -7,6 +7,9 @@ launch-collapse as the training step, applied to serving.
 
     pred = Predictor(model, points=8192, batch=1, iters=32)
     flow = pred(xyz1, xyz2)   # (B, N, 3)
+
+    # flow for every point of full-resolution clouds (batch-1 predictors):
+    dense = pred.predict_dense(pc1_full, pc2_full, k=3)   # (n1, 3)
 """
 
 from __future__ import annotations
@@ -79,3 +82,50 @@ class Predictor:
         self._graph.replay()
         self.last_flows = self._flows
         return self._flows[-1].clone()
+
+    @torch.no_grad()
+    def predict_dense(self, pc1_full: torch.Tensor, pc2_full: torch.Tensor, k: int = 3,
+                      generator: Optional[torch.Generator] = None,
+                      return_sparse: bool = False):
+        """Flow for EVERY point of ``pc1_full`` ((n1,3) or (1,n1,3)).
+
+        Draws ``points`` indices without replacement from each full cloud
+        (``torch.randperm`` with ``generator``, so a seeded generator makes
+        the call reproducible), runs the fixed-shape forward on the samples
+        (graph replay as in ``__call__``), then interpolates the sparse flow
+        onto the full cloud with ``ops.knn_interpolate`` -- eagerly, outside
+        the captured graph, because n1 differs per sample.
+
+        Returns flow (n1, 3) in ``pc1_full``'s dtype on the predictor's
+        device; with ``return_sparse`` the tuple (flow, idx1, flow_sub):
+        idx1 (points,) int64 indices into pc1_full and the sparse flow
+        flow_sub (points, 3) predicted at them.
+        """
+        from pvraft_amd import ops
+
+        batch, points = self._in1.shape[0], self._in1.shape[1]
+        if batch != 1:
+            raise ValueError(f"predict_dense needs a batch-1 Predictor, this one has batch={batch}")
+        clouds = []
+        for name, pc in (("pc1_full", pc1_full), ("pc2_full", pc2_full)):
+            if pc.dim() == 3 and pc.shape[0] == 1:
+                pc = pc[0]
+            if pc.dim() != 2 or pc.shape[1] != 3:
+                raise ValueError(f"{name} must be (n,3) or (1,n,3), got {tuple(pc.shape)}")
+            if pc.shape[0] < points:
+                raise ValueError(
+                    f"{name} has {pc.shape[0]} points, fewer than the {points} the predictor samples"
+                )
+            clouds.append(pc.to(self.device))
+        gdev = generator.device if generator is not None else torch.device("cpu")
+        subs, idxs = [], []
+        for pc in clouds:
+            idx = torch.randperm(pc.shape[0], generator=generator, device=gdev)[:points].to(self.device)
+            idxs.append(idx)
+            subs.append(pc[idx].float().unsqueeze(0))
+        flow_sub = self(subs[0], subs[1])  # (1, points, 3)
+        dense, _, _ = ops.knn_interpolate(subs[0], flow_sub, clouds[0].float().unsqueeze(0), k)
+        dense = dense[0].to(pc1_full.dtype)
+        if return_sparse:
+            return dense, idxs[0], flow_sub[0]
+        return dense

@@ -495,6 +495,67 @@ def knn_graph(xyz: Tensor, k: int) -> Tensor:
     return reference.knn_idx(xyz, k)
 
 
+class _KnnInterpolate(torch.autograd.Function):
+    """Fused cross-set kNN + inverse-distance blend (csrc/knn_interp.hip).
+    Neighbours and weights are constants to autograd; the backward is a
+    scatter of w * dout into the selected support rows."""
+
+    @staticmethod
+    def forward(ctx, support_xyz, values, query_xyz, k, eps):
+        out, idx32, w = _EXT.knn_interp_fwd(support_xyz, values, query_xyz, k, eps)
+        idx = idx32.long()
+        ctx.save_for_backward(idx, w)
+        ctx.n_support = values.shape[1]
+        ctx.mark_non_differentiable(idx, w)
+        return out, idx, w
+
+    @staticmethod
+    def backward(ctx, dout, _didx, _dw):
+        idx, w = ctx.saved_tensors
+        B, M, ke = idx.shape
+        C = dout.shape[2]
+        # empty slots (-1, weight 0: non-finite coordinates) add zeros to row 0
+        rows = (idx.clamp_min(0) + torch.arange(B, device=idx.device).view(B, 1, 1) * ctx.n_support).reshape(-1)
+        contrib = (w.unsqueeze(-1) * dout.unsqueeze(2)).reshape(B * M * ke, C)
+        dvalues = torch.zeros(B * ctx.n_support, C, dtype=dout.dtype, device=dout.device)
+        dvalues.index_add_(0, rows, contrib)
+        return None, dvalues.view(B, ctx.n_support, C), None, None, None
+
+
+def knn_interpolate(
+    support_xyz: Tensor, values: Tensor, query_xyz: Tensor, k: int = 3, eps: float = 1e-8
+) -> Tuple[Tensor, Tensor, Tensor]:
+    """Inverse-distance interpolation of ``values`` from a support cloud
+    onto query points: (B,N,3),(B,N,C),(B,M,3) -> out (B,M,C), idx
+    (B,M,k_eff) int64, w (B,M,k_eff), k_eff = min(k, N), 1 <= k <= 16.
+
+    w_i = 1/(d2_i + eps) normalised over the k_eff nearest support points
+    (idx ascending in distance), out = sum_i w_i * values[idx_i].  The
+    (M, N) distance matrix is never materialised.  bf16/fp16 or
+    non-contiguous inputs are upcast / made contiguous here.
+
+    Autograd flows to ``values`` only; coordinates get no gradient.  On
+    GPU the backward is an ``index_add_`` over the saved (idx, w), whose
+    atomic accumulation order is NON-DETERMINISTIC (last-bit run-to-run
+    differences in ``values.grad``).
+    """
+    if not 1 <= int(k) <= 16:
+        raise ValueError(f"knn_interpolate requires 1 <= k <= 16, got {k}")
+    if _use_hip(support_xyz):
+        return _KnnInterpolate.apply(
+            support_xyz.detach().float().contiguous(),
+            values.float().contiguous(),
+            query_xyz.detach().float().contiguous(),
+            int(k),
+            float(eps),
+        )
+    if not (support_xyz.dtype == values.dtype == query_xyz.dtype == torch.float64):
+        support_xyz, values, query_xyz = support_xyz.float(), values.float(), query_xyz.float()
+    return reference.knn_interpolate(
+        support_xyz.detach().contiguous(), values.contiguous(), query_xyz.detach().contiguous(), int(k), float(eps)
+    )
+
+
 def gather_edge_concat(feats: Tensor, idx: Tensor, xyz: Tensor, csr=None) -> Tensor:
     """(B,N,C),(B,N,K),(B,N,3) -> (B,C+3,K,N) edge-conv input.
 

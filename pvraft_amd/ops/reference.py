@@ -10,6 +10,7 @@ the reference implementation (weiyithu/PV-RAFT):
   + top-K truncation   -> reference model/corr.py:31-42,95-99
 * voxel correlation    -> reference model/corr.py:47-73 (torch_scatter there)
 * kNN correlation      -> reference model/corr.py:75-93
+* kNN interpolation    -> absent in the reference (dense-flow propagation)
 
 Unlike the reference, nothing here ever materialises the full B x N x N
 distance / correlation matrix in one piece: all O(N^2) sites are chunked over
@@ -47,6 +48,59 @@ def knn_idx(xyz: Tensor, k: int, chunk: int = 4096) -> Tensor:
         d = sq[:, s : s + chunk].unsqueeze(-1) + sq.unsqueeze(1) - 2.0 * torch.bmm(q, xyz.transpose(1, 2))
         out.append(d.topk(k, dim=-1, largest=False).indices)
     return torch.cat(out, dim=1)
+
+
+def knn_interpolate(
+    support_xyz: Tensor,
+    values: Tensor,
+    query_xyz: Tensor,
+    k: int = 3,
+    eps: float = 1e-8,
+    chunk: int = 4096,
+) -> Tuple[Tensor, Tensor, Tensor]:
+    """Inverse-distance kNN interpolation from a support cloud onto queries
+    (absent in the reference; the PointNet++-style feature propagation
+    step, used to carry the sparse flow to the full-resolution cloud).
+
+    support_xyz: (B, N, 3), values: (B, N, C), query_xyz: (B, M, 3).
+    Returns (out (B, M, C), idx (B, M, k_eff) int64, w (B, M, k_eff)) with
+    k_eff = min(k, N):
+
+      d2_i = |q - s_i|^2 from coordinate differences (no |a|^2+|b|^2-2ab
+             expansion, which cancels catastrophically for near points)
+      w_i  = 1 / (d2_i + eps), normalised to sum to 1 over the k_eff
+      out  = sum_i w_i * values[idx_i]
+
+    idx is sorted by ascending distance.  Neighbour selection and weights
+    are constants to autograd; gradient flows to ``values`` only.  Chunked
+    over queries so only a (B, chunk, N) distance slab is ever alive.
+    """
+    if not 1 <= k <= 16:
+        raise ValueError(f"knn_interpolate requires 1 <= k <= 16, got {k}")
+    B, N, _ = support_xyz.shape
+    M = query_xyz.shape[1]
+    C = values.shape[2]
+    ke = min(k, N)
+    outs, idxs, ws = [], [], []
+    with torch.no_grad():
+        sx = support_xyz[..., 0].unsqueeze(1)  # B, 1, N
+        sy = support_xyz[..., 1].unsqueeze(1)
+        sz = support_xyz[..., 2].unsqueeze(1)
+    for s in range(0, M, chunk):
+        with torch.no_grad():
+            q = query_xyz[:, s : s + chunk]  # B, m, 3
+            d2 = (q[..., 0:1] - sx) ** 2
+            d2 += (q[..., 1:2] - sy) ** 2
+            d2 += (q[..., 2:3] - sz) ** 2  # B, m, N
+            d, i = d2.topk(ke, dim=-1, largest=False, sorted=True)
+            w = 1.0 / (d + eps)
+            w = w / w.sum(-1, keepdim=True)
+        m = i.shape[1]
+        nb = values.gather(1, i.reshape(B, m * ke, 1).expand(B, m * ke, C)).view(B, m, ke, C)
+        outs.append((w.unsqueeze(-1).to(values.dtype) * nb).sum(2))
+        idxs.append(i)
+        ws.append(w)
+    return torch.cat(outs, dim=1), torch.cat(idxs, dim=1), torch.cat(ws, dim=1)
 
 
 def gather_edge_concat(feats: Tensor, idx: Tensor, xyz: Tensor) -> Tensor:

@@ -18,6 +18,8 @@ def parse_args():
     add_common_args(parser, training=False)
     parser.add_argument("--gamma", help="exponential weights", default=0.8, type=float)
     parser.add_argument("--dump_results", help="write result/<dataset>/<i>/{pc1,pc2,flow}.npy for visual.py", action="store_true")
+    parser.add_argument("--dense", help="also interpolate the flow onto the full-resolution pc1 and report dense_* metrics", action="store_true")
+    parser.add_argument("--dense_k", help="neighbours for the dense interpolation", default=3, type=int)
     return parser.parse_args()
 
 

@@ -4,7 +4,9 @@ which renders pc1/pc2/pc1+flow with mayavi; here matplotlib 3D -> PNG,
 since mayavi is not in this environment).
 
 Reads <root>/result/<dataset>/<index>/{pc1,pc2,flow}.npy as written by
-``test.py --dump_results`` and writes view.png alongside.
+``test.py --dump_results`` and writes view.png alongside.  When the run
+was ``--dense`` ({pc1_full,flow_dense}.npy exist) the full-resolution
+cloud and its dense flow are rendered instead of the sampled pair.
 
     python visual.py --index 0 --dataset FT3D --root ./
 """
@@ -28,6 +30,10 @@ def main():
     pc1 = np.load(os.path.join(d, "pc1.npy")).reshape(-1, 3)
     pc2 = np.load(os.path.join(d, "pc2.npy")).reshape(-1, 3)
     flow = np.load(os.path.join(d, "flow.npy")).reshape(-1, 3)
+    # test.py --dense: render the full-resolution cloud and its dense flow
+    if os.path.exists(os.path.join(d, "flow_dense.npy")):
+        pc1 = np.load(os.path.join(d, "pc1_full.npy")).reshape(-1, 3)
+        flow = np.load(os.path.join(d, "flow_dense.npy")).reshape(-1, 3)
 
     import matplotlib
 
