@@ -2,7 +2,8 @@
 
 All reference flags are preserved; MI355X-native additions: --amp (bf16
 autocast), --num_workers, --dataset SYNTH (synthetic pairs, no data on
-disk needed).  --gpus keeps the reference semantics of selecting devices
+disk needed), --self_supervised with --chamfer_weight / --smooth_weight /
+--smooth_k (training only).  --gpus keeps the reference semantics of selecting devices
 but launches one process per GPU (torch.distributed over RCCL) instead of
 DataParallel: when more than one GPU is requested and the process is not
 already under torchrun, the CLI re-execs itself through
@@ -59,6 +60,14 @@ def add_common_args(parser: argparse.ArgumentParser, training: bool) -> None:
         parser.add_argument("--batch_size", help="global mini-batch size", default=1, type=int)
         parser.add_argument("--num_epochs", help="number of epochs for training", default=20, type=int)
         parser.add_argument("--checkpoint_interval", help="save checkpoint every N epoch", default=5, type=int)
+        parser.add_argument(
+            "--self_supervised",
+            help="train on Chamfer + flow-smoothness loss (no ground-truth flow in the loss)",
+            action="store_true",
+        )
+        parser.add_argument("--chamfer_weight", help="self-supervised Chamfer weight", default=1.0, type=float)
+        parser.add_argument("--smooth_weight", help="self-supervised smoothness weight", default=1.0, type=float)
+        parser.add_argument("--smooth_k", help="neighbours in the smoothness graph", default=9, type=int)
 
 
 def maybe_relaunch_distributed(args, script: str) -> bool:

@@ -7,6 +7,20 @@ void launch_knn_graph(const float*, int*, int, int, int, hipStream_t);
 void launch_knn_interp(const float*, const float*, const float*, float*, int*,
                        float*, int, int, int, int, int, float, hipStream_t);
 int knn_interp_tile_pts();
+void launch_chamfer_fwd(const float*, const float*, const float*, float*, int*,
+                        float*, int*, float*, int, int, int, int, int,
+                        hipStream_t);
+void launch_chamfer_bwd(const float*, const float*, const float*, const int*,
+                        const int*, const float*, float*, int, int, int, int,
+                        hipStream_t);
+int chamfer_fwd_blocks(int, int, int);
+int chamfer_tile_pts();
+void launch_flow_smooth_fwd(const float*, const int*, float*, int, int, int,
+                            int, hipStream_t);
+void launch_flow_smooth_bwd(const float*, const int*, const int*, const int*,
+                            const float*, float*, int, int, int, int,
+                            hipStream_t);
+int flow_smooth_blocks(int);
 void launch_morton_keys(const float*, const float*, const float*, long*,
                         int, long, hipStream_t);
 void launch_gather_edge_fwd(const void*, const int*, const float*, void*,
@@ -1171,7 +1185,165 @@ std::vector<torch::Tensor> seq_loss_bwd(std::vector<torch::Tensor> flows,
   return grads;
 }
 
+static void check_i32(const torch::Tensor& t, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.is_contiguous() && t.scalar_type() == torch::kInt32,
+              name, " must be a contiguous int32 GPU tensor");
+}
+
+// shared shape / range checks of the Chamfer entry points
+static void chamfer_check(const torch::Tensor& pc1, const torch::Tensor& pc2,
+                          int64_t T) {
+  check_f32(pc1, "pc1");
+  check_f32(pc2, "pc2");
+  TORCH_CHECK(pc1.dim() == 3 && pc1.size(2) == 3, "pc1 must be (B,N,3)");
+  TORCH_CHECK(pc2.dim() == 3 && pc2.size(2) == 3, "pc2 must be (B,M,3)");
+  TORCH_CHECK(pc2.device() == pc1.device(), "chamfer inputs must share a device");
+  const int64_t B = pc1.size(0), N = pc1.size(1), M = pc2.size(1);
+  TORCH_CHECK(pc2.size(0) == B, "chamfer batch mismatch");
+  TORCH_CHECK(T >= 1 && T <= 32, "chamfer supports 1..32 flows");
+  TORCH_CHECK(B >= 1 && B <= 65535 && N >= 1 && M >= 1,
+              "chamfer requires 1 <= B <= 65535, N, M >= 1");
+  TORCH_CHECK(N < (1L << 31) - 256 && M < (1L << 31) - 256,
+              "chamfer sizes exceed 32-bit point indexing");
+}
+
+// pc1 (B,N,3), flows (T,B,N,3), pc2 (B,M,3), all fp32 contiguous ->
+// {chamfer (T) f32, d2_1 (T,B,N) f32, idx_1 (T,B,N) i32, d2_2 (T,B,M) f32,
+//  idx_2 (T,B,M) i32}
+std::vector<torch::Tensor> chamfer_fwd(torch::Tensor pc1, torch::Tensor flows,
+                                       torch::Tensor pc2) {
+  check_f32(flows, "flows");
+  TORCH_CHECK(flows.dim() == 4, "flows must be (T,B,N,3)");
+  const int64_t T = flows.size(0);
+  chamfer_check(pc1, pc2, T);
+  const int64_t B = pc1.size(0), N = pc1.size(1), M = pc2.size(1);
+  TORCH_CHECK(flows.size(1) == B && flows.size(2) == N && flows.size(3) == 3 &&
+                  flows.device() == pc1.device(),
+              "flows must be (T,B,N,3) on the device of pc1");
+  auto fopt = pc1.options();
+  auto iopt = fopt.dtype(torch::kInt32);
+  auto d1 = torch::empty({T, B, N}, fopt);
+  auto i1 = torch::empty({T, B, N}, iopt);
+  auto d2 = torch::empty({T, B, M}, fopt);
+  auto i2 = torch::empty({T, B, M}, iopt);
+  const int nblk = chamfer_fwd_blocks((int)N, (int)M, 2);
+  // blocks past the end of the smaller cloud write nothing: zero-filled
+  auto part = torch::zeros({T, 2, B * (int64_t)nblk}, fopt);
+  launch_chamfer_fwd(pc1.data_ptr<float>(), flows.data_ptr<float>(),
+                     pc2.data_ptr<float>(), d1.data_ptr<float>(),
+                     i1.data_ptr<int>(), d2.data_ptr<float>(),
+                     i2.data_ptr<int>(), part.data_ptr<float>(), (int)B, (int)N,
+                     (int)M, (int)T, 2, stream());
+  auto sums = part.sum(2);  // (T, 2), deterministic fold of the block sums
+  auto cham = sums.select(1, 0) / (double)(B * N) + sums.select(1, 1) / (double)(B * M);
+  return {cham, d1, i1, d2, i2};
+}
+
+// one direction, no flow: query (B,Q,3), support (B,S,3) -> {d2 (B,Q), idx (B,Q) i32}
+std::vector<torch::Tensor> chamfer_nn_fwd(torch::Tensor query,
+                                          torch::Tensor support) {
+  chamfer_check(query, support, 1);
+  const int64_t B = query.size(0), Q = query.size(1), S = support.size(1);
+  auto d = torch::empty({B, Q}, query.options());
+  auto i = torch::empty({B, Q}, query.options().dtype(torch::kInt32));
+  const int nblk = chamfer_fwd_blocks((int)Q, (int)S, 1);
+  auto part = torch::empty({B * (int64_t)nblk}, query.options());
+  launch_chamfer_fwd(query.data_ptr<float>(), nullptr,
+                     support.data_ptr<float>(), d.data_ptr<float>(),
+                     i.data_ptr<int>(), nullptr, nullptr,
+                     part.data_ptr<float>(), (int)B, (int)Q, (int)S, 1, 1,
+                     stream());
+  return {d, i};
+}
+
+// gradient of sum_t g_t * chamfer_t with respect to the flows
+torch::Tensor chamfer_bwd(torch::Tensor pc1, torch::Tensor flows,
+                          torch::Tensor pc2, torch::Tensor idx1,
+                          torch::Tensor idx2, torch::Tensor gout) {
+  check_f32(flows, "flows");
+  check_f32(gout, "grad");
+  check_i32(idx1, "idx1");
+  check_i32(idx2, "idx2");
+  TORCH_CHECK(flows.dim() == 4, "flows must be (T,B,N,3)");
+  const int64_t T = flows.size(0);
+  chamfer_check(pc1, pc2, T);
+  const int64_t B = pc1.size(0), N = pc1.size(1), M = pc2.size(1);
+  TORCH_CHECK(flows.size(1) == B && flows.size(2) == N && flows.size(3) == 3,
+              "flows must be (T,B,N,3)");
+  TORCH_CHECK(idx1.numel() == T * B * N && idx2.numel() == T * B * M &&
+                  gout.numel() == T,
+              "chamfer_bwd index / gradient shape mismatch");
+  TORCH_CHECK(flows.device() == pc1.device() && idx1.device() == pc1.device() &&
+                  idx2.device() == pc1.device() && gout.device() == pc1.device(),
+              "chamfer_bwd inputs must share a device");
+  auto dflow = torch::empty_like(flows);
+  launch_chamfer_bwd(pc1.data_ptr<float>(), flows.data_ptr<float>(),
+                     pc2.data_ptr<float>(), idx1.data_ptr<int>(),
+                     idx2.data_ptr<int>(), gout.data_ptr<float>(),
+                     dflow.data_ptr<float>(), (int)B, (int)N, (int)M, (int)T,
+                     stream());
+  return dflow;
+}
+
+static void flow_smooth_check(const torch::Tensor& flows,
+                              const torch::Tensor& idx) {
+  check_f32(flows, "flows");
+  check_i32(idx, "idx");
+  TORCH_CHECK(flows.dim() == 4 && flows.size(3) == 3, "flows must be (T,B,N,3)");
+  TORCH_CHECK(idx.dim() == 3, "idx must be (B,N,k)");
+  const int64_t T = flows.size(0), B = flows.size(1), N = flows.size(2);
+  TORCH_CHECK(idx.size(0) == B && idx.size(1) == N && idx.device() == flows.device(),
+              "idx must be (B,N,k) on the device of flows");
+  TORCH_CHECK(T >= 1 && T <= 32, "flow_smooth supports 1..32 flows");
+  TORCH_CHECK(B >= 1 && B <= 65535 && N >= 1 && idx.size(2) >= 1,
+              "flow_smooth requires 1 <= B <= 65535, N, k >= 1");
+  TORCH_CHECK(N * idx.size(2) < (1L << 31) - 256,
+              "flow_smooth sizes exceed 32-bit edge indexing");
+}
+
+// flows (T,B,N,3) f32, idx (B,N,k) i32 -> smooth (T)
+torch::Tensor flow_smooth_fwd(torch::Tensor flows, torch::Tensor idx) {
+  flow_smooth_check(flows, idx);
+  const int64_t T = flows.size(0), B = flows.size(1), N = flows.size(2);
+  const int64_t k = idx.size(2);
+  const int nblk = flow_smooth_blocks((int)N);
+  auto part = torch::empty({T, B * (int64_t)nblk}, flows.options());
+  launch_flow_smooth_fwd(flows.data_ptr<float>(), idx.data_ptr<int>(),
+                         part.data_ptr<float>(), (int)B, (int)N, (int)k, (int)T,
+                         stream());
+  return part.sum(1) / (double)(B * N * k);
+}
+
+torch::Tensor flow_smooth_bwd(torch::Tensor flows, torch::Tensor idx,
+                              torch::Tensor offsets, torch::Tensor order_n,
+                              torch::Tensor gout) {
+  flow_smooth_check(flows, idx);
+  check_i32(offsets, "offsets");
+  check_i32(order_n, "order_n");
+  check_f32(gout, "grad");
+  const int64_t T = flows.size(0), B = flows.size(1), N = flows.size(2);
+  const int64_t k = idx.size(2);
+  TORCH_CHECK(offsets.numel() == B * (N + 1) && order_n.numel() == B * N * k &&
+                  gout.numel() == T,
+              "flow_smooth_bwd CSR / gradient shape mismatch");
+  TORCH_CHECK(offsets.device() == flows.device() && order_n.device() == flows.device() &&
+                  gout.device() == flows.device(),
+              "flow_smooth_bwd inputs must share a device");
+  auto dflow = torch::empty_like(flows);
+  launch_flow_smooth_bwd(flows.data_ptr<float>(), idx.data_ptr<int>(),
+                         offsets.data_ptr<int>(), order_n.data_ptr<int>(),
+                         gout.data_ptr<float>(), dflow.data_ptr<float>(), (int)B,
+                         (int)N, (int)k, (int)T, stream());
+  return dflow;
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  m.def("chamfer_fwd", &chamfer_fwd);
+  m.def("chamfer_nn_fwd", &chamfer_nn_fwd);
+  m.def("chamfer_bwd", &chamfer_bwd);
+  m.attr("CHAMFER_TILE") = chamfer_tile_pts();
+  m.def("flow_smooth_fwd", &flow_smooth_fwd);
+  m.def("flow_smooth_bwd", &flow_smooth_bwd);
   m.def("topk_rows", &topk_rows);
   m.def("corr_topk", &corr_topk);
   m.def("seq_loss_fwd", &seq_loss_fwd);

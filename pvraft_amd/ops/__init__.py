@@ -841,3 +841,107 @@ def gru_q(pre_q: Tensor, z: Tensor, h: Tensor) -> Tensor:
             pre_q.contiguous(), z.contiguous(), h.to(pre_q.dtype).contiguous()
         )
     return (1 - z) * h + z * torch.tanh(pre_q)
+
+
+# ---------------------------------------------------------------------------
+# self-supervised loss terms (csrc/chamfer.hip, csrc/flow_smooth.hip)
+# ---------------------------------------------------------------------------
+
+
+class _ChamferLoss(torch.autograd.Function):
+    """Fused Chamfer distance of T warped clouds (csrc/chamfer.hip): one
+    launch for all flows and both directions; the backward is a
+    deterministic gather over the saved assignments."""
+
+    @staticmethod
+    def forward(ctx, pc1, flows, pc2):
+        cham, _d1, i1, _d2, i2 = _EXT.chamfer_fwd(pc1, flows, pc2)
+        ctx.save_for_backward(pc1, flows, pc2, i1, i2)
+        return cham
+
+    @staticmethod
+    def backward(ctx, g):
+        pc1, flows, pc2, i1, i2 = ctx.saved_tensors
+        return None, _EXT.chamfer_bwd(pc1, flows, pc2, i1, i2, g.float().contiguous()), None
+
+
+class _FlowSmoothness(torch.autograd.Function):
+    """Fused smoothness of T flows over one kNN graph
+    (csrc/flow_smooth.hip); the backward walks the graph's inverse
+    adjacency, so it needs no atomics."""
+
+    @staticmethod
+    def forward(ctx, flows, idx32, offsets, order_n):
+        ctx.save_for_backward(flows, idx32, offsets, order_n)
+        return _EXT.flow_smooth_fwd(flows, idx32)
+
+    @staticmethod
+    def backward(ctx, g):
+        flows, idx32, offsets, order_n = ctx.saved_tensors
+        return _EXT.flow_smooth_bwd(flows, idx32, offsets, order_n, g.float().contiguous()), None, None, None
+
+
+def _fp32_unless_all_fp64(*tensors: Tensor):
+    if all(t.dtype == torch.float64 for t in tensors):
+        return tensors
+    return tuple(t.float() for t in tensors)
+
+
+def chamfer_nn(query: Tensor, support: Tensor) -> Tuple[Tensor, Tensor]:
+    """Nearest support point of every query: (B,Q,3), (B,S,3) -> d2 (B,Q),
+    idx (B,Q) int64.  Squared distances from coordinate differences; ties go
+    to the lowest index; a NaN or +INF distance never wins, and a query with
+    no finite candidate gets idx -1 and d2 = +INF.  Not differentiable.
+    The (Q, S) distance matrix is never materialised.  bf16/fp16 or
+    non-contiguous inputs are upcast / made contiguous here.
+    """
+    if _use_hip(query):
+        d2, idx32 = _EXT.chamfer_nn_fwd(
+            query.detach().float().contiguous(), support.detach().float().contiguous()
+        )
+        return d2, idx32.long()
+    query, support = _fp32_unless_all_fp64(query.detach(), support.detach())
+    return reference.chamfer_nn(query.contiguous(), support.contiguous())
+
+
+def chamfer_loss(pc1: Tensor, flows, pc2: Tensor) -> Tensor:
+    """Chamfer distance between every warped cloud ``pc1 + f_t`` and
+    ``pc2``: pc1 (B,N,3), flows = (T,B,N,3), a list of T (B,N,3) tensors or
+    one (B,N,3) tensor, pc2 (B,M,3) -> (T,), 1 <= T <= 32,
+
+      chamfer_t = mean_{b,i} min_j |w_t[b,i] - pc2[b,j]|^2
+                + mean_{b,j} min_i |pc2[b,j] - w_t[b,i]|^2
+
+    with the nearest-neighbour rules of ``chamfer_nn``.  Autograd flows to
+    the flows only; coordinates get no gradient.  The GPU backward is
+    deterministic (no atomics).
+    """
+    flows = reference.stack_flows(flows)
+    if not 1 <= flows.shape[0] <= 32:
+        raise ValueError(f"chamfer_loss supports 1..32 flows, got {flows.shape[0]}")
+    if _use_hip(pc1):
+        return _ChamferLoss.apply(
+            pc1.detach().float().contiguous(), flows.float().contiguous(), pc2.detach().float().contiguous()
+        )
+    pc1, flows, pc2 = _fp32_unless_all_fp64(pc1.detach(), flows, pc2.detach())
+    return reference.chamfer_loss(pc1.contiguous(), flows.contiguous(), pc2.contiguous())
+
+
+def flow_smoothness(flows, graph) -> Tensor:
+    """Mean squared flow difference along the edges of ``graph`` (a
+    ``model.graph.Graph`` over pc1, self edges included): flows as in
+    ``chamfer_loss`` -> (T,),
+
+      smooth_t = mean_{b,i,j in idx[b,i]} |f_t[b,j] - f_t[b,i]|^2
+
+    Autograd flows to the flows only; the GPU backward is deterministic.
+    """
+    flows = reference.stack_flows(flows)
+    if not 1 <= flows.shape[0] <= 32:
+        raise ValueError(f"flow_smoothness supports 1..32 flows, got {flows.shape[0]}")
+    if _use_hip(flows):
+        _, offsets, order_n, _ = graph.csr()
+        return _FlowSmoothness.apply(flows.float().contiguous(), graph.idx32, offsets, order_n)
+    if flows.dtype != torch.float64:
+        flows = flows.float()
+    return reference.flow_smoothness(flows.contiguous(), graph.idx)

@@ -235,3 +235,87 @@ def knn_corr(corr: Tensor, xyz: Tensor, coords: Tensor, k: int) -> Tensor:
     kx = xyz.gather(2, nbr.unsqueeze(-1).expand(B, N, k, 3))  # B, N, k, 3
     rel = (kx - coords.unsqueeze(2)).permute(0, 3, 2, 1)  # B, 3, k, N
     return torch.cat([kc, rel], dim=1)
+
+
+# ---------------------------------------------------------------------------
+# Self-supervised loss terms (absent in the reference): nearest neighbour
+# across two clouds, Chamfer distance of warped clouds, flow smoothness
+# ---------------------------------------------------------------------------
+
+
+def stack_flows(flows) -> Tensor:
+    """A (B,N,3) flow, a list of them or a (T,B,N,3) stack -> (T,B,N,3)."""
+    if isinstance(flows, (list, tuple)):
+        return torch.stack(list(flows), dim=0)
+    return flows.unsqueeze(0) if flows.dim() == 3 else flows
+
+
+def chamfer_nn(query: Tensor, support: Tensor, chunk: int = 1024) -> Tuple[Tensor, Tensor]:
+    """Nearest support point of every query: (B,Q,3), (B,S,3) -> d2 (B,Q),
+    idx (B,Q) int64.
+
+    d2 from coordinate differences; ties go to the lowest index; a NaN or
+    +INF distance never wins; a query with no finite candidate gets idx -1
+    and d2 = +INF.  Not differentiable.  Chunked over queries so only a
+    (B, chunk, S) distance slab is ever alive.
+    """
+    ds, idxs = [], []
+    with torch.no_grad():
+        sx = support[..., 0].unsqueeze(1)  # B, 1, S
+        sy = support[..., 1].unsqueeze(1)
+        sz = support[..., 2].unsqueeze(1)
+        for s in range(0, query.shape[1], chunk):
+            q = query[:, s : s + chunk]
+            d2 = (q[..., 0:1] - sx) ** 2
+            d2 += (q[..., 1:2] - sy) ** 2
+            d2 += (q[..., 2:3] - sz) ** 2  # B, q, S
+            d2 = torch.where(torch.isfinite(d2), d2, torch.full_like(d2, float("inf")))
+            i = d2.argmin(dim=-1)  # first of equal minima
+            d = d2.gather(2, i.unsqueeze(-1)).squeeze(-1)
+            idxs.append(torch.where(torch.isfinite(d), i, torch.full_like(i, -1)))
+            ds.append(d)
+    return torch.cat(ds, dim=1), torch.cat(idxs, dim=1)
+
+
+def _matched_d2(query: Tensor, support: Tensor) -> Tensor:
+    """Differentiable squared distance of every query to its (constant)
+    nearest support point; 0 where there is none.  (B,Q)"""
+    _, idx = chamfer_nn(query, support)
+    valid = idx >= 0
+    B, Q = idx.shape
+    near = support.gather(1, idx.clamp_min(0).unsqueeze(-1).expand(B, Q, 3))
+    zero = torch.zeros_like(query)
+    diff = torch.where(valid.unsqueeze(-1), query, zero) - torch.where(valid.unsqueeze(-1), near, zero)
+    return (diff * diff).sum(-1)
+
+
+def chamfer_loss(pc1: Tensor, flows, pc2: Tensor) -> Tensor:
+    """Chamfer distance between each warped cloud pc1 + f_t and pc2:
+    pc1 (B,N,3), flows (T,B,N,3) or a list, pc2 (B,M,3) -> (T,),
+
+      chamfer_t = mean_{b,i} min_j |w_t[b,i] - pc2[b,j]|^2
+                + mean_{b,j} min_i |pc2[b,j] - w_t[b,i]|^2
+
+    The assignments are constants to autograd.
+    """
+    flows = stack_flows(flows)
+    out = []
+    for f in flows:
+        w = pc1 + f
+        out.append(_matched_d2(w, pc2).mean() + _matched_d2(pc2, w).mean())
+    return torch.stack(out)
+
+
+def flow_smoothness(flows, idx: Tensor) -> Tensor:
+    """Mean squared flow difference along the edges of a kNN graph:
+    flows (T,B,N,3) or a list, idx (B,N,k) -> (T,),
+
+      smooth_t = mean_{b,i,j in idx[b,i]} |f_t[b,j] - f_t[b,i]|^2
+    """
+    flows = stack_flows(flows)
+    T, B, N, _ = flows.shape
+    k = idx.shape[-1]
+    flat = idx.reshape(1, B, N * k, 1).expand(T, B, N * k, 3)
+    nb = flows.gather(2, flat).view(T, B, N, k, 3)
+    d = nb - flows.unsqueeze(3)
+    return (d * d).sum(-1).mean(dim=(1, 2, 3))

@@ -1,4 +1,4 @@
-from .loss import compute_loss, sequence_loss
+from .loss import compute_loss, self_supervised_loss, sequence_loss
 from .metrics import compute_epe, compute_epe_train
 from .checkpoint import (
     save_checkpoint,

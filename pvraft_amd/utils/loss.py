@@ -3,11 +3,13 @@
 compute_loss: masked mean-L1 between estimated and ground-truth flow
 (loss.py:34-38).  sequence_loss: exponentially weighted sum over the
 per-iteration predictions, weight gamma^(T-1-i) (loss.py:8-11).
+self_supervised_loss (absent in the reference): the same gamma weighting of
+Chamfer distance + flow smoothness, which needs no ground-truth flow.
 """
 
 from __future__ import annotations
 
-from typing import List, Sequence
+from typing import List, Sequence, Union
 
 import torch
 from torch import Tensor
@@ -83,3 +85,37 @@ def _eager_loss(est_flow: Tensor, batch) -> Tensor:
     total = (error.abs() * m.unsqueeze(-1)).sum()
     count = m.sum() * error.shape[-1]
     return total / count.clamp(min=1)
+
+
+def self_supervised_loss(
+    est_flow: Union[Tensor, Sequence[Tensor]],
+    batch,
+    gamma: float = 0.8,
+    chamfer_weight: float = 1.0,
+    smooth_weight: float = 1.0,
+    smooth_k: int = 9,
+    graph=None,
+) -> Tensor:
+    """Label-free scene-flow objective over the T per-iteration flows,
+
+      loss = sum_t gamma^(T-1-t) * (chamfer_weight * chamfer_t + smooth_weight * smooth_t)
+
+    chamfer_t: Chamfer distance between pc1 + f_t and pc2 (ops.chamfer_loss);
+    smooth_t: mean squared flow difference over pc1's smooth_k-NN graph
+    (ops.flow_smoothness).  Reads only batch["sequence"]; ``graph`` may pass
+    a prebuilt ``Graph`` of pc1.  ``est_flow`` is one flow or a sequence.
+    """
+    from pvraft_amd import ops
+    from pvraft_amd.model.graph import Graph
+
+    pc1, pc2 = batch["sequence"]
+    flows = ops.reference.stack_flows(est_flow)
+    if graph is None:
+        graph = Graph.build(pc1.detach(), min(int(smooth_k), pc1.shape[1]))
+    chamfer = ops.chamfer_loss(pc1, flows, pc2)
+    smooth = ops.flow_smoothness(flows, graph)
+    n = flows.shape[0]
+    weights = torch.tensor(
+        [gamma ** (n - 1 - t) for t in range(n)], dtype=chamfer.dtype, device=chamfer.device
+    )
+    return (weights * (chamfer_weight * chamfer + smooth_weight * smooth.to(chamfer.dtype))).sum()

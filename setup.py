@@ -32,6 +32,8 @@ SOURCES = [
     "pvraft_amd/csrc/corr_topk.hip",
     "pvraft_amd/csrc/gru_gates.hip",
     "pvraft_amd/csrc/seq_loss.hip",
+    "pvraft_amd/csrc/chamfer.hip",
+    "pvraft_amd/csrc/flow_smooth.hip",
 ]
 
 setup(
