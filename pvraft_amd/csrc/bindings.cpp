@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 
 void launch_knn_graph(const float*, int*, int, int, int, hipStream_t);
+void launch_knn_csr(const int*, int*, int*, int*, int*, int*, unsigned char*,
+                    int, int, int, hipStream_t);
 void launch_knn_interp(const float*, const float*, const float*, float*, int*,
                        float*, int, int, int, int, int, float, hipStream_t);
 int knn_interp_tile_pts();
@@ -86,7 +88,7 @@ void launch_egnmp_fwd(const void*, const int*, float*, float*, float*,
                       unsigned char*, unsigned char*, float*, void*,
                       unsigned char*, float*,
                       int, long, int, int, int, float, int, float,
-                      const float*, bool, int, hipStream_t);
+                      const float*, bool, int, bool, hipStream_t);
 void launch_egnmp_bwd(const void*, const void*, const int*,
                       const unsigned char*, const float*, const float*,
                       const int*, const int*,
@@ -102,7 +104,7 @@ void launch_kg_fwd(const float*, const float*, const float*, float*, float*,
                    float*, float*, const float*, const float*, float*,
                    float*, unsigned char*, unsigned char*, void*,
                    unsigned char*, float*, int, long, int, int, int, float,
-                   const float*, bool, int, hipStream_t);
+                   const float*, bool, int, bool, hipStream_t);
 void launch_kg_bwd(const void*, const float*, const float*, const float*,
                    const unsigned char*, const float*, const float*,
                    const float*, const float*, const float*, float*, float*,
@@ -191,6 +193,32 @@ torch::Tensor knn_graph(torch::Tensor xyz, int64_t k) {
   launch_knn_graph(xyz.data_ptr<float>(), out.data_ptr<int>(), B, N, (int)k,
                    stream());
   return out;
+}
+
+// idx32 (B,N,k) int32 contiguous -> {order (B,k*N) i32, offsets (B,N+1) i32,
+// order_n (B,k*N) i32, order_j (B,k*N) u8}: edge ids j*N+n sorted by
+// (target, id) -- the inverse adjacency of the kNN graph (csrc/knn_csr.hip)
+std::vector<torch::Tensor> knn_csr(torch::Tensor idx32) {
+  TORCH_CHECK(idx32.is_cuda() && idx32.is_contiguous() && idx32.dim() == 3 &&
+              idx32.scalar_type() == torch::kInt32,
+              "idx32 must be a contiguous (B,N,k) int32 GPU tensor");
+  const int64_t B = idx32.size(0), N = idx32.size(1), k = idx32.size(2);
+  TORCH_CHECK(k >= 1 && k <= 48, "knn_csr requires 1 <= k <= 48");
+  TORCH_CHECK(B >= 1 && B <= 65535 && N >= 1 && k * N < (1L << 31) - 256,
+              "knn_csr requires 1 <= B <= 65535, N >= 1, k*N < 2^31");
+  auto iopt = idx32.options();
+  auto order = torch::empty({B, k * N}, iopt);
+  auto offsets = torch::empty({B, N + 1}, iopt);
+  auto order_n = torch::empty({B, k * N}, iopt);
+  auto order_j = torch::empty({B, k * N}, iopt.dtype(torch::kUInt8));
+  auto bucket = torch::empty({B, k * N}, iopt);
+  auto cnt = zeros_fast({B, N}, iopt);
+  launch_knn_csr(idx32.data_ptr<int>(), cnt.data_ptr<int>(),
+                 bucket.data_ptr<int>(), order.data_ptr<int>(),
+                 offsets.data_ptr<int>(), order_n.data_ptr<int>(),
+                 order_j.data_ptr<unsigned char>(), (int)B, (int)N, (int)k,
+                 stream());
+  return {order, offsets, order_n, order_j};
 }
 
 // support (B,N,3), values (B,N,C), query (B,M,3), all fp32 contiguous ->
@@ -541,12 +569,14 @@ std::vector<torch::Tensor> group_norm_act_maxpool_bwd(
 // SetConv stage 1 on the linearly-restructured operands: wg (B, N, M)
 // point-major = (fc1 W @ [feats; xyz]) per point; pooled output y and u8
 // argmax are point-major too.  GN stats over the full (M/G, K, N) edge
-// extent, identical to group_norm_act_maxpool.
+// extent, identical to group_norm_act_maxpool.  channel_major_out: y is
+// written (B, M, N) instead (am/vsel stay point-major for the backward).
 std::vector<torch::Tensor> edge_gnmp_fwd(torch::Tensor wg, torch::Tensor idx,
                                          int64_t G, torch::Tensor weight,
                                          torch::Tensor bias, double eps,
                                          int64_t act, double slope,
-                                         c10::optional<torch::Tensor> slope_t) {
+                                         c10::optional<torch::Tensor> slope_t,
+                                         bool channel_major_out = false) {
   const float* slope_ptr = nullptr;
   if (act == 2) {
     TORCH_CHECK(slope_t.has_value() && slope_t->numel() == 1, "act=2 needs a scalar slope tensor");
@@ -571,7 +601,8 @@ std::vector<torch::Tensor> edge_gnmp_fwd(torch::Tensor wg, torch::Tensor idx,
   auto scratch = torch::empty({(long)rows * 2, (long)rchunks * B}, fopt);
   auto mean = torch::empty({rows}, fopt);
   auto rstd = torch::empty({rows}, fopt);
-  auto y = torch::empty_like(wg);
+  auto y = channel_major_out ? torch::empty({B, (long)M, N}, wg.options())
+                             : torch::empty_like(wg);
   auto am = torch::empty({B, N, M}, wg.options().dtype(torch::kUInt8));
   // per-(n, c) gather extremes tracked by the reduce pass (the pick pass
   // is elementwise; the second full gather sweep is gone).  fp32: the
@@ -594,7 +625,7 @@ std::vector<torch::Tensor> edge_gnmp_fwd(torch::Tensor wg, torch::Tensor idx,
                    y.data_ptr(),
                    am.data_ptr<unsigned char>(), vsel.data_ptr<float>(), B, N,
                    K, M, (int)G, (float)eps, (int)act, (float)slope,
-                   slope_ptr, bf16, rchunks, stream());
+                   slope_ptr, bf16, rchunks, channel_major_out, stream());
   return {y, am, vsel, vsum, mean, rstd};
 }
 
@@ -654,7 +685,8 @@ std::vector<torch::Tensor> knn_gnmp_fwd(torch::Tensor raw, torch::Tensor W,
                                         torch::Tensor gamma,
                                         torch::Tensor beta, double eps,
                                         torch::Tensor slope_t,
-                                        bool out_bf16) {
+                                        bool out_bf16,
+                                        bool channel_major_out = false) {
   check_f32(raw, "raw");
   check_f32(W, "W");
   check_f32(cb, "cb");
@@ -689,9 +721,10 @@ std::vector<torch::Tensor> knn_gnmp_fwd(torch::Tensor raw, torch::Tensor W,
   auto amax = torch::empty({B, N, C}, raw.options().dtype(torch::kUInt8));
   auto amin = torch::empty({B, N, C}, raw.options().dtype(torch::kUInt8));
   auto am = torch::empty({B, N, C}, raw.options().dtype(torch::kUInt8));
-  auto y = torch::empty({B, N, C}, raw.options().dtype(
-                                       out_bf16 ? torch::kBFloat16
-                                                : torch::kFloat32));
+  auto yopt = raw.options().dtype(out_bf16 ? torch::kBFloat16
+                                           : torch::kFloat32);
+  auto y = channel_major_out ? torch::empty({B, (long)C, N}, yopt)
+                             : torch::empty({B, N, (long)C}, yopt);
   launch_kg_fwd(raw.data_ptr<float>(), W.data_ptr<float>(),
                 cb.data_ptr<float>(), scratch.data_ptr<float>(),
                 ws.data_ptr<float>(), mean.data_ptr<float>(),
@@ -701,7 +734,7 @@ std::vector<torch::Tensor> knn_gnmp_fwd(torch::Tensor raw, torch::Tensor W,
                 amin.data_ptr<unsigned char>(), y.data_ptr(),
                 am.data_ptr<unsigned char>(), vsel.data_ptr<float>(), B, N,
                 K, C, (int)G, (float)eps, slope_t.data_ptr<float>(),
-                out_bf16, nblk, stream());
+                out_bf16, nblk, channel_major_out, stream());
   return {y, am, vsel, mean, rstd};
 }
 
@@ -816,14 +849,15 @@ std::vector<torch::Tensor> pw_wgrad(torch::Tensor dy, torch::Tensor x,
 
 // Fused MFMA 1x1-conv forward: y = act(sum_i W_i @ x_i + bias + addend)
 // in one launch (csrc/pw_fwd.hip)
-void launch_pw_fwd(const void**, const void**, const int*, int, const float*,
-                   const void*, long, int, void*, int, int, long, int,
-                   hipStream_t);
+void launch_pw_fwd(const void**, const void**, const int*, const int*, int,
+                   const float*, const void*, long, int, void*, int, int, long,
+                   int, int, hipStream_t);
 
 torch::Tensor pw_fwd(std::vector<torch::Tensor> ws,
                      std::vector<torch::Tensor> xs,
                      c10::optional<torch::Tensor> bias,
-                     c10::optional<torch::Tensor> addend, int64_t act) {
+                     c10::optional<torch::Tensor> addend, int64_t act,
+                     bool point_major = false) {
   const int n = (int)ws.size();
   TORCH_CHECK(n >= 1 && n <= 4 && (int)xs.size() == n, "1..4 parts");
   const int Co = ws[0].size(0);
@@ -832,9 +866,14 @@ torch::Tensor pw_fwd(std::vector<torch::Tensor> ws,
   const void* wp[4];
   const void* xp[4];
   int cis[4];
+  int lds[4];
   for (int i = 0; i < n; ++i) {
-    TORCH_CHECK(ws[i].is_cuda() && ws[i].is_contiguous() && ws[i].dim() == 2 &&
-                ws[i].scalar_type() == torch::kBFloat16, "w must be (Co,Ci) bf16");
+    // rows contiguous, any row pitch: column slices of a wider weight
+    TORCH_CHECK(ws[i].is_cuda() && ws[i].dim() == 2 &&
+                (ws[i].size(1) == 1 || ws[i].stride(1) == 1) &&
+                (ws[i].size(0) == 1 || ws[i].stride(0) >= ws[i].size(1)) &&
+                ws[i].scalar_type() == torch::kBFloat16,
+                "w must be (Co,Ci) bf16 with contiguous rows");
     TORCH_CHECK(xs[i].is_cuda() && xs[i].is_contiguous() && xs[i].dim() == 3 &&
                 xs[i].scalar_type() == torch::kBFloat16, "x must be (B,Ci,S) bf16");
     TORCH_CHECK(ws[i].size(0) == Co && xs[i].size(0) == B && xs[i].size(2) == S);
@@ -843,6 +882,7 @@ torch::Tensor pw_fwd(std::vector<torch::Tensor> ws,
     wp[i] = ws[i].data_ptr();
     xp[i] = xs[i].data_ptr();
     cis[i] = (int)ws[i].size(1);
+    lds[i] = ws[i].size(0) == 1 ? cis[i] : (int)ws[i].stride(0);
   }
   TORCH_CHECK(Co <= 256, "pw_fwd: Co <= 256");
   const float* bptr = nullptr;
@@ -865,9 +905,11 @@ torch::Tensor pw_fwd(std::vector<torch::Tensor> ws,
     aptr = a.data_ptr();
     abstride = a.stride(0);
   }
-  auto y = torch::empty({B, (long)Co, S}, xs[0].options());
-  launch_pw_fwd(wp, xp, cis, n, bptr, aptr, abstride, afp32, y.data_ptr(), B,
-                Co, S, (int)act, stream());
+  // point_major: y is written (B, S, Co) straight from the epilogue
+  auto y = point_major ? torch::empty({B, S, (long)Co}, xs[0].options())
+                       : torch::empty({B, (long)Co, S}, xs[0].options());
+  launch_pw_fwd(wp, xp, cis, lds, n, bptr, aptr, abstride, afp32, y.data_ptr(), B,
+                Co, S, (int)act, point_major ? 1 : 0, stream());
   return y;
 }
 
@@ -904,10 +946,18 @@ std::vector<torch::Tensor> pw_wgrad_batched(std::vector<torch::Tensor> dys,
     TORCH_CHECK(x.is_cuda() && x.is_contiguous() && x.dim() == 3 &&
                 x.scalar_type() == torch::kBFloat16, "x must be (B,Ci,S) bf16");
     TORCH_CHECK(dy.size(0) == x.size(0) && dy.size(2) == x.size(2), "dy/x mismatch");
-    TORCH_CHECK(dw.is_cuda() && dw.is_contiguous() &&
-                dw.scalar_type() == torch::kFloat32, "dw must be contiguous fp32");
+    // flat contiguous, or a (Co, Ci) column block of a wider grad buffer
+    // (rows contiguous, row pitch >= Ci)
+    const bool dw_block = dw.dim() == 2 && !dw.is_contiguous();
+    TORCH_CHECK(dw.is_cuda() && dw.scalar_type() == torch::kFloat32 &&
+                (dw_block ? (dw.stride(1) == 1 && dw.stride(0) >= dw.size(1))
+                          : dw.is_contiguous()),
+                "dw must be fp32, contiguous or a row-contiguous block");
     const int Co = dy.size(1), Ci = x.size(1);
-    TORCH_CHECK(dw.numel() == (long)Co * Ci, "dw numel mismatch");
+    TORCH_CHECK(dw.numel() == (long)Co * Ci &&
+                (!dw_block || (dw.size(0) == Co && dw.size(1) == Ci)),
+                "dw shape mismatch");
+    const int ldw = dw_block ? (int)dw.stride(0) : Ci;
     TORCH_CHECK(Co <= 16 * TILE && Ci <= 16 * TILE, "Co/Ci too large for 4-bit tile index");
     float* dbias = nullptr;
     if (dbs[j].defined() && dbs[j].numel() > 0) {
@@ -916,7 +966,8 @@ std::vector<torch::Tensor> pw_wgrad_batched(std::vector<torch::Tensor> dys,
       dbias = dbs[j].data_ptr<float>();
     }
     jobs[j] = PwWgradJob{dy.data_ptr(), x.data_ptr(), dw.data_ptr<float>(),
-                         dbias, Co, Ci, (int)dy.size(0), 1, dy.size(2)};
+                         dbias, Co, Ci, (int)dy.size(0), 1, dy.size(2), ldw,
+                         0};
     base_blocks += (long)((Co + TILE - 1) / TILE) * ((Ci + TILE - 1) / TILE) *
                    dy.size(0);
   }
@@ -1356,19 +1407,30 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("pv_corr_fused_bwd", &pv_corr_fused_bwd);
   m.def("pw_wgrad", &pw_wgrad, pybind11::arg("dy"), pybind11::arg("x"), pybind11::arg("schunks") = 0, pybind11::arg("with_bias") = false);
   m.def("pw_wgrad_batched", &pw_wgrad_batched);
-  m.def("pw_fwd", &pw_fwd);
+  m.def("pw_fwd", &pw_fwd, pybind11::arg("ws"), pybind11::arg("xs"),
+        pybind11::arg("bias"), pybind11::arg("addend"), pybind11::arg("act"),
+        pybind11::arg("point_major") = false);
   m.def("batched_transpose", &batched_transpose);
   m.def("group_norm_act_fwd", &group_norm_act_fwd);
   m.def("group_norm_act_bwd", &group_norm_act_bwd);
   m.def("group_norm_act_maxpool_fwd", &group_norm_act_maxpool_fwd);
   m.def("group_norm_act_maxpool_bwd", &group_norm_act_maxpool_bwd);
-  m.def("edge_gnmp_fwd", &edge_gnmp_fwd);
+  m.def("edge_gnmp_fwd", &edge_gnmp_fwd, pybind11::arg("wg"),
+        pybind11::arg("idx"), pybind11::arg("G"), pybind11::arg("weight"),
+        pybind11::arg("bias"), pybind11::arg("eps"), pybind11::arg("act"),
+        pybind11::arg("slope"), pybind11::arg("slope_t"),
+        pybind11::arg("channel_major_out") = false);
   m.def("edge_gnmp_bwd", &edge_gnmp_bwd);
   m.def("morton_keys", &morton_keys);
   m.def("multi_cast_bf16", &multi_cast_bf16);
-  m.def("knn_gnmp_fwd", &knn_gnmp_fwd);
+  m.def("knn_gnmp_fwd", &knn_gnmp_fwd, pybind11::arg("raw"),
+        pybind11::arg("W"), pybind11::arg("cb"), pybind11::arg("G"),
+        pybind11::arg("gamma"), pybind11::arg("beta"), pybind11::arg("eps"),
+        pybind11::arg("slope_t"), pybind11::arg("out_bf16"),
+        pybind11::arg("channel_major_out") = false);
   m.def("knn_gnmp_bwd", &knn_gnmp_bwd);
   m.def("knn_graph", &knn_graph, "fused kNN graph (CDNA4)");
+  m.def("knn_csr", &knn_csr, "inverse kNN adjacency as CSR (counting sort)");
   m.def("knn_interp_fwd", &knn_interp_fwd);
   m.attr("KNN_INTERP_TILE") = knn_interp_tile_pts();
   m.def("gather_edge_concat_fwd", &gather_edge_concat_fwd);

@@ -24,9 +24,10 @@
 // Layout: Wg is stored point-major, wg[b, n, m] ("WgT"), so a neighbour
 // gather reads a contiguous M-vector; every thread owns a 4-channel quad
 // (8 B bf16 / 16 B fp32 vector loads) and threads of one point cover
-// adjacent quads (coalesced).  Outputs y/argmax are point-major too; the
-// caller transposes the 3 MB pooled result with the LDS-tiled transpose
-// kernel (trivial next to the 100 MB it replaces).
+// adjacent quads (coalesced).  The argmax and the saved extremes are
+// point-major too (the backward reads them that way); the pooled result y
+// is written point-major or, for callers that consume (B, M, N), straight
+// channel-major through an LDS tile (egnmp_fwd_pick_cm_kernel).
 //
 // Reductions are DETERMINISTIC: each block writes its partial sums to a
 // per-block scratch slot (no global atomics); the forward GN stats fold
@@ -76,7 +77,9 @@ struct alignas(4 * sizeof(T)) Quad {
 
 // pass 1: per-block partial sum/sumsq per group over all (c, j, n)
 // gather-diff elements -> scratch[(out)*(gridX*B) + gx*B + b], out in
-// [0, G*2).  Deterministic (no atomics past the LDS bins).
+// [0, G*2).  Deterministic: the LDS bins are kept PER WAVE (a wave's own
+// atomics retire in program/lane order; across waves the order would
+// depend on scheduling) and folded in wave order.
 // ... and, per (n, c), the EXTREMES of v over j with their arg j: the
 // activation(GN(v)) is piecewise monotone in v (pre = v*(rstd*gamma) +
 // const; LeakyReLU/PReLU monotone per sign region), so the K-max-pool
@@ -104,9 +107,11 @@ __global__ __launch_bounds__(EG_THREADS) void egnmp_fwd_reduce_kernel(
   const int Cg = M / G;
   const int n_out = B * G * 2;
 
-  extern __shared__ float bins[];  // (B*G*2); only this block's b is used
-  for (unsigned i = threadIdx.x; i < (unsigned)n_out; i += EG_THREADS)
+  extern __shared__ float bins[];  // (waves, B*G*2); only this block's b
+  constexpr int NW = EG_THREADS / WAVE;
+  for (unsigned i = threadIdx.x; i < (unsigned)(n_out * NW); i += EG_THREADS)
     bins[i] = 0.f;
+  float *wbins = bins + wave_id() * n_out;
   __syncthreads();
 
   const T *wgb = wg + (long)b * N * M;
@@ -161,15 +166,19 @@ __global__ __launch_bounds__(EG_THREADS) void egnmp_fwd_reduce_kernel(
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const int g = (c4 * 4 + e) / Cg;
-      atomicAdd(&bins[(b * G + g) * 2 + 0], s[e]);
-      atomicAdd(&bins[(b * G + g) * 2 + 1], ss[e]);
+      atomicAdd(&wbins[(b * G + g) * 2 + 0], s[e]);
+      atomicAdd(&wbins[(b * G + g) * 2 + 1], ss[e]);
     }
   }
   __syncthreads();
   const long col = (long)blockIdx.x * B + b;
   const long stride = (long)gridDim.x * B;
-  for (unsigned i = threadIdx.x; i < (unsigned)n_out; i += EG_THREADS)
-    scratch[i * stride + col] = bins[i];
+  for (unsigned i = threadIdx.x; i < (unsigned)n_out; i += EG_THREADS) {
+    float v = bins[i];
+#pragma unroll
+    for (int w = 1; w < NW; ++w) v += bins[w * n_out + i];
+    scratch[i * stride + col] = v;
+  }
 }
 
 // fold per-block partials into ws: one wave per output slot.  Slots that
@@ -192,6 +201,51 @@ __global__ void egnmp_sum_partials_kernel(const float *__restrict__ scratch,
 // arg j (act(gn(v)) is piecewise monotone in v, so the max over all K
 // values is attained at one of the two extremes, for either sign of
 // gamma and any activation slope).
+// one 4-channel quad of the pick: shared by both output layouts so they
+// are the same arithmetic
+template <typename T, int ACT>
+DEV_INLINE void egnmp_pick_quad(
+    const float *__restrict__ vmax, const float *__restrict__ vmin,
+    const unsigned char *__restrict__ amax,
+    const unsigned char *__restrict__ amin,
+    const float *__restrict__ mean, const float *__restrict__ rstd,
+    const float *__restrict__ gamma, const float *__restrict__ beta,
+    unsigned char *__restrict__ am, float *__restrict__ vsel, long i, int b,
+    int c0, int Cg, int G, float slope, Quad<T> &oq) {
+  const float4 qx = *(const float4 *)(vmax + i);
+  const float4 qn = *(const float4 *)(vmin + i);
+  const uchar4 ax = *(const uchar4 *)(amax + i);
+  const uchar4 an = *(const uchar4 *)(amin + i);
+  const float qxs[4] = {qx.x, qx.y, qx.z, qx.w};
+  const float qns[4] = {qn.x, qn.y, qn.z, qn.w};
+  const int axs[4] = {ax.x, ax.y, ax.z, ax.w};
+  const int ans[4] = {an.x, an.y, an.z, an.w};
+  float sq[4];
+  uchar4 aq;
+  unsigned char out_j[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const int c = c0 + e;
+    const int row = b * G + c / Cg;
+    const float m = mean[row];
+    const float r = rstd[row];
+    const float ga = gamma[c], be = beta[c];
+    float vhi = (qxs[e] - m) * r * ga + be;
+    float vlo = (qns[e] - m) * r * ga + be;
+    if (ACT >= 1) {
+      vhi = vhi > 0.f ? vhi : vhi * slope;
+      vlo = vlo > 0.f ? vlo : vlo * slope;
+    }
+    const bool hi = vhi >= vlo;
+    oq.v[e] = (T)(hi ? vhi : vlo);
+    sq[e] = hi ? qxs[e] : qns[e];
+    out_j[e] = (unsigned char)(hi ? axs[e] : ans[e]);
+  }
+  aq.x = out_j[0]; aq.y = out_j[1]; aq.z = out_j[2]; aq.w = out_j[3];
+  *(uchar4 *)(am + i) = aq;
+  *(float4 *)(vsel + i) = make_float4(sq[0], sq[1], sq[2], sq[3]);
+}
+
 template <typename T, int ACT>
 __global__ __launch_bounds__(EG_THREADS) void egnmp_fwd_pick_kernel(
     const float *__restrict__ vmax, const float *__restrict__ vmin,
@@ -209,43 +263,113 @@ __global__ __launch_bounds__(EG_THREADS) void egnmp_fwd_pick_kernel(
   for (long i4 = (long)blockIdx.x * EG_THREADS + threadIdx.x; i4 * 4 < total;
        i4 += (long)gridDim.x * EG_THREADS) {
     const long i = i4 * 4;
-    const long b = i / NM;
-    const int c0 = (int)(i % M);
-    const float4 qx = *(const float4 *)(vmax + i);
-    const float4 qn = *(const float4 *)(vmin + i);
-    const uchar4 ax = *(const uchar4 *)(amax + i);
-    const uchar4 an = *(const uchar4 *)(amin + i);
-    const float qxs[4] = {qx.x, qx.y, qx.z, qx.w};
-    const float qns[4] = {qn.x, qn.y, qn.z, qn.w};
-    const int axs[4] = {ax.x, ax.y, ax.z, ax.w};
-    const int ans[4] = {an.x, an.y, an.z, an.w};
     Quad<T> oq;
-    float sq[4];
-    uchar4 aq;
-    unsigned char out_j[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int c = c0 + e;
-      const int row = (int)b * G + c / Cg;
-      const float m = mean[row];
-      const float r = rstd[row];
-      const float ga = gamma[c], be = beta[c];
-      float vhi = (qxs[e] - m) * r * ga + be;
-      float vlo = (qns[e] - m) * r * ga + be;
-      if (ACT >= 1) {
-        vhi = vhi > 0.f ? vhi : vhi * slope;
-        vlo = vlo > 0.f ? vlo : vlo * slope;
-      }
-      const bool hi = vhi >= vlo;
-      oq.v[e] = (T)(hi ? vhi : vlo);
-      sq[e] = hi ? qxs[e] : qns[e];
-      out_j[e] = (unsigned char)(hi ? axs[e] : ans[e]);
-    }
-    aq.x = out_j[0]; aq.y = out_j[1]; aq.z = out_j[2]; aq.w = out_j[3];
+    egnmp_pick_quad<T, ACT>(vmax, vmin, amax, amin, mean, rstd, gamma, beta,
+                            am, vsel, i, (int)(i / NM), (int)(i % M), Cg, G,
+                            slope, oq);
     *(Quad<T> *)(y + i) = oq;
-    *(uchar4 *)(am + i) = aq;
-    *(float4 *)(vsel + i) = make_float4(sq[0], sq[1], sq[2], sq[3]);
   }
+}
+
+// channel-major output mode: the same pick, but y lands as (B, M, N) so the
+// callers' transpose of the pooled result disappears.  One block owns
+// PICK_TP<T> consecutive points of one batch (a contiguous point-major
+// span: coalesced reads, am/vsel written in place as above) and stages y
+// through an LDS tile [M][PICK_TP + pad]; the tile then drains as runs of
+// consecutive n within each channel.
+template <typename T>
+struct PickTile {
+  static constexpr int TP = sizeof(T) == 2 ? 64 : 32;  // points per block
+  static constexpr int PITCH = TP + (sizeof(T) == 2 ? 2 : 1);  // odd dwords
+};
+
+template <typename T, int ACT>
+__global__ __launch_bounds__(EG_THREADS) void egnmp_fwd_pick_cm_kernel(
+    const float *__restrict__ vmax, const float *__restrict__ vmin,
+    const unsigned char *__restrict__ amax,
+    const unsigned char *__restrict__ amin,
+    const float *__restrict__ mean, const float *__restrict__ rstd,
+    const float *__restrict__ gamma, const float *__restrict__ beta,
+    T *__restrict__ y,               // (B, M, N)
+    unsigned char *__restrict__ am,  // (B, N, M)
+    float *__restrict__ vsel,        // (B, N, M)
+    long N, int M, int G, float slope, const float *__restrict__ slope_ptr) {
+  constexpr int TP = PickTile<T>::TP;
+  constexpr int PITCH = PickTile<T>::PITCH;
+  extern __shared__ __align__(16) unsigned char pick_smem[];
+  T *tile = (T *)pick_smem;  // (M, PITCH)
+  if (ACT == 2) slope = *slope_ptr;
+  const int b = blockIdx.y;
+  const long n0 = (long)blockIdx.x * TP;
+  const int np = (int)((N - n0) < TP ? (N - n0) : TP);  // points in tile
+  const int Cg = M / G;
+  const int tpc = M / 4;  // quads per point
+  const long base = ((long)b * N + n0) * M;
+  for (int q = threadIdx.x; q < np * tpc; q += EG_THREADS) {
+    const int p = q / tpc;
+    const int c0 = (q - p * tpc) * 4;
+    Quad<T> oq;
+    egnmp_pick_quad<T, ACT>(vmax, vmin, amax, amin, mean, rstd, gamma, beta,
+                            am, vsel, base + (long)q * 4, b, c0, Cg, G, slope,
+                            oq);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) tile[(c0 + e) * PITCH + p] = oq.v[e];
+  }
+  __syncthreads();
+  T *yb = y + (long)b * M * N + n0;
+  for (int i = threadIdx.x; i < M * TP; i += EG_THREADS) {
+    const int c = i / TP;
+    const int p = i - c * TP;
+    if (p < np) yb[(long)c * N + p] = tile[c * PITCH + p];
+  }
+}
+
+template <typename T, int ACT>
+static void egnmp_pick_launch(const float *vmax, const float *vmin,
+                              const unsigned char *amax,
+                              const unsigned char *amin, const float *mean,
+                              const float *rstd, const float *gamma,
+                              const float *beta, T *y, unsigned char *am,
+                              float *vsel, int B, long N, int M, int G,
+                              float slope, const float *slope_ptr,
+                              bool channel_major, hipStream_t stream) {
+  if (channel_major) {
+    constexpr int TP = PickTile<T>::TP;
+    const dim3 grid((unsigned)((N + TP - 1) / TP), B);
+    const size_t shmem = (size_t)M * PickTile<T>::PITCH * sizeof(T);
+    hipLaunchKernelGGL((egnmp_fwd_pick_cm_kernel<T, ACT>), grid,
+                       dim3(EG_THREADS), shmem, stream, vmax, vmin, amax, amin,
+                       mean, rstd, gamma, beta, y, am, vsel, N, M, G, slope,
+                       slope_ptr);
+    return;
+  }
+  const long total = (long)B * N * M;
+  long pb = (total / 4 + EG_THREADS - 1) / EG_THREADS;
+  if (pb > 2048) pb = 2048;
+  if (pb < 1) pb = 1;
+  hipLaunchKernelGGL((egnmp_fwd_pick_kernel<T, ACT>), dim3((unsigned)pb),
+                     dim3(EG_THREADS), 0, stream, vmax, vmin, amax, amin, mean,
+                     rstd, gamma, beta, y, am, vsel, total, N * M, M, G, slope,
+                     slope_ptr);
+}
+
+template <typename T>
+static void egnmp_pick_dispatch(const float *vmax, const float *vmin,
+                                const unsigned char *amax,
+                                const unsigned char *amin, const float *mean,
+                                const float *rstd, const float *gamma,
+                                const float *beta, T *y, unsigned char *am,
+                                float *vsel, int B, long N, int M, int G,
+                                int act, float slope, const float *slope_ptr,
+                                bool channel_major, hipStream_t stream) {
+#define EG_PICK(A)                                                            \
+  egnmp_pick_launch<T, A>(vmax, vmin, amax, amin, mean, rstd, gamma, beta, y, \
+                          am, vsel, B, N, M, G, slope, slope_ptr,             \
+                          channel_major, stream)
+  if (act == 2) EG_PICK(2);
+  else if (act == 1) EG_PICK(1);
+  else EG_PICK(0);
+#undef EG_PICK
 }
 
 // ---------------------------------------------------------------- backward
@@ -273,10 +397,13 @@ __global__ __launch_bounds__(EG_THREADS) void egnmp_bwd_reduce_kernel(
   const int Cg = M / G;
   if (ACT == 2) slope = *slope_ptr;
 
-  extern __shared__ float sbins[];  // [G*2*B rows | M*2 chans | 1 slope]
+  // per wave: [G*2*B rows | M*2 chans | 1 slope] (see the forward reduce)
+  extern __shared__ float sbins_all[];
+  constexpr int NW = EG_THREADS / WAVE;
   const int n_out = G * 2 * B + M * 2 + 1;
-  for (unsigned i = threadIdx.x; i < (unsigned)n_out; i += EG_THREADS)
-    sbins[i] = 0.f;
+  for (unsigned i = threadIdx.x; i < (unsigned)(n_out * NW); i += EG_THREADS)
+    sbins_all[i] = 0.f;
+  float *sbins = sbins_all + wave_id() * n_out;
   __syncthreads();
 
   const T *wgb = wg + (long)b * N * M;
@@ -333,8 +460,12 @@ __global__ __launch_bounds__(EG_THREADS) void egnmp_bwd_reduce_kernel(
   __syncthreads();
   const long col = (long)blockIdx.x * B + b;
   const long stride = (long)gridDim.x * B;
-  for (unsigned i = threadIdx.x; i < (unsigned)n_out; i += EG_THREADS)
-    scratch[i * stride + col] = sbins[i];
+  for (unsigned i = threadIdx.x; i < (unsigned)n_out; i += EG_THREADS) {
+    float v = sbins_all[i];
+#pragma unroll
+    for (int w = 1; w < NW; ++w) v += sbins_all[w * n_out + i];
+    scratch[i * stride + col] = v;
+  }
 }
 
 // pass 2: dWgT (B, N, M), deterministic.  The centre term
@@ -470,28 +601,19 @@ void egnmp_fwd_impl(const T *wg, const int *idx, float *scratch, float *ws,
                     unsigned char *am, float *vsel,
                     int B, long N, int K, int M, int G, float eps, int act,
                     float slope, const float *slope_ptr, int rchunks,
-                    hipStream_t stream) {
+                    bool channel_major, hipStream_t stream) {
   const dim3 rgrid(rchunks, 1, B);
   const int n_out_f = B * G * 2;
   hipLaunchKernelGGL(egnmp_fwd_reduce_kernel<T>, rgrid, dim3(EG_THREADS),
-                     (size_t)n_out_f * sizeof(float), stream, wg, idx,
+                     (size_t)n_out_f * (EG_THREADS / WAVE) * sizeof(float),
+                     stream, wg, idx,
                      scratch, vmax, vmin, amax, amin, vsum, N, K, M, G);
   (void)ws;
   launch_gn_finalize_scratch(scratch, (long)rchunks * B, mean, rstd,
                              (long)(M / G) * K * N, B * G, eps, stream);
-  const long total = (long)B * N * M;
-  long pb = (total / 4 + EG_THREADS - 1) / EG_THREADS;
-  if (pb > 2048) pb = 2048;
-  if (pb < 1) pb = 1;
-#define EG_FWD(A)                                                             \
-  hipLaunchKernelGGL((egnmp_fwd_pick_kernel<T, A>), dim3((unsigned)pb),       \
-                     dim3(EG_THREADS), 0, stream, vmax, vmin, amax, amin,     \
-                     mean, rstd, gamma, beta, y, am, vsel, total,             \
-                     N * M, M, G, slope, slope_ptr)
-  if (act == 2) EG_FWD(2);
-  else if (act == 1) EG_FWD(1);
-  else EG_FWD(0);
-#undef EG_FWD
+  egnmp_pick_dispatch<T>(vmax, vmin, amax, amin, mean, rstd, gamma, beta, y,
+                         am, vsel, B, N, M, G, act, slope, slope_ptr,
+                         channel_major, stream);
 }
 
 template <typename T>
@@ -510,7 +632,7 @@ void egnmp_bwd_impl(const T *dy, const T *wg, const int *idx,
   const dim3 rgrid(rchunks, 1, B);
   const dim3 agrid(eg_chunks(N, ppb, B, 2048), 1, B);
   const int n_out = B * G * 2 + M * 2 + 1;
-  const size_t shmem = (size_t)n_out * sizeof(float);
+  const size_t shmem = (size_t)n_out * (EG_THREADS / WAVE) * sizeof(float);
   const long row_len = (long)(M / G) * K * N;
   const int waves_per_block = EG_THREADS / WAVE;
 #define EG_BWD(A)                                                              \
@@ -541,28 +663,18 @@ void launch_gnmp_pick(const float *vmax, const float *vmin,
                       const unsigned char *amax, const unsigned char *amin,
                       const float *mean, const float *rstd,
                       const float *gamma, const float *beta, void *y,
-                      unsigned char *am, float *vsel, long total, long NM,
-                      int M, int G, int act, float slope,
-                      const float *slope_ptr, bool bf16,
-                      hipStream_t stream) {
-  long pb = (total / 4 + EG_THREADS - 1) / EG_THREADS;
-  if (pb > 2048) pb = 2048;
-  if (pb < 1) pb = 1;
-#define EG_PICK(T, A)                                                         \
-  hipLaunchKernelGGL((egnmp_fwd_pick_kernel<T, A>), dim3((unsigned)pb),       \
-                     dim3(EG_THREADS), 0, stream, vmax, vmin, amax, amin,     \
-                     mean, rstd, gamma, beta, (T *)y, am, vsel, total, NM,    \
-                     M, G, slope, slope_ptr)
-  if (bf16) {
-    if (act == 2) EG_PICK(__hip_bfloat16, 2);
-    else if (act == 1) EG_PICK(__hip_bfloat16, 1);
-    else EG_PICK(__hip_bfloat16, 0);
-  } else {
-    if (act == 2) EG_PICK(float, 2);
-    else if (act == 1) EG_PICK(float, 1);
-    else EG_PICK(float, 0);
-  }
-#undef EG_PICK
+                      unsigned char *am, float *vsel, int B, long N, int M,
+                      int G, int act, float slope, const float *slope_ptr,
+                      bool bf16, bool channel_major, hipStream_t stream) {
+  if (bf16)
+    egnmp_pick_dispatch<__hip_bfloat16>(vmax, vmin, amax, amin, mean, rstd,
+                                        gamma, beta, (__hip_bfloat16 *)y, am,
+                                        vsel, B, N, M, G, act, slope,
+                                        slope_ptr, channel_major, stream);
+  else
+    egnmp_pick_dispatch<float>(vmax, vmin, amax, amin, mean, rstd, gamma,
+                               beta, (float *)y, am, vsel, B, N, M, G, act,
+                               slope, slope_ptr, channel_major, stream);
 }
 
 int egnmp_reduce_chunks(long N, int M, int B) {
@@ -581,7 +693,7 @@ void launch_egnmp_fwd(const void *wg, const int *idx, float *scratch,
                       void *y, unsigned char *am, float *vsel, int B, long N,
                       int K, int M, int G, float eps, int act, float slope,
                       const float *slope_ptr, bool bf16, int rchunks,
-                      hipStream_t stream) {
+                      bool channel_major, hipStream_t stream) {
   if (bf16)
     egnmp_fwd_impl<__hip_bfloat16>((const __hip_bfloat16 *)wg, idx, scratch,
                                    ws, mean, rstd, gamma, beta,
@@ -589,12 +701,13 @@ void launch_egnmp_fwd(const void *wg, const int *idx, float *scratch,
                                    (__hip_bfloat16 *)y, am,
                                    vsel, B, N, K,
                                    M, G, eps, act, slope, slope_ptr, rchunks,
-                                   stream);
+                                   channel_major, stream);
   else
     egnmp_fwd_impl<float>((const float *)wg, idx, scratch, ws, mean, rstd,
                           gamma, beta, vmax, vmin, amax,
                           amin, vsum, (float *)y, am, vsel, B, N, K,
-                          M, G, eps, act, slope, slope_ptr, rchunks, stream);
+                          M, G, eps, act, slope, slope_ptr, rchunks,
+                          channel_major, stream);
 }
 
 void launch_egnmp_bwd(const void *dy, const void *wg, const int *idx,

@@ -47,8 +47,8 @@ __global__ void egnmp_sum_partials_kernel(const float *__restrict__,
 void launch_gnmp_pick(const float *, const float *, const unsigned char *,
                       const unsigned char *, const float *, const float *,
                       const float *, const float *, void *, unsigned char *,
-                      float *, long, long, int, int, int, float,
-                      const float *, bool, hipStream_t);
+                      float *, int, long, int, int, int, float,
+                      const float *, bool, bool, hipStream_t);
 
 // ---------------------------------------------------------------- forward
 
@@ -79,8 +79,12 @@ __global__ __launch_bounds__(KG_THREADS) void kg_fwd_reduce_kernel(
     br[c] = cb[c0 + c];
   }
 
-  __shared__ float bins[8 * 2];  // (NG<=8, 2): this block's group sums
-  if (threadIdx.x < (unsigned)(NG * 2)) bins[threadIdx.x] = 0.f;
+  // (waves, NG<=8, 2): this block's group sums, kept per wave and folded
+  // in wave order so the result does not depend on wave scheduling
+  constexpr int NW = KG_THREADS / WAVE;
+  __shared__ float bins[NW * 16];
+  if (threadIdx.x < (unsigned)(NW * 16)) bins[threadIdx.x] = 0.f;
+  float *wbins = bins + wave_id() * 16;
   __syncthreads();
 
   const float *rawb = raw + (long)b * 4 * K * N;
@@ -146,8 +150,8 @@ __global__ __launch_bounds__(KG_THREADS) void kg_fwd_reduce_kernel(
 #pragma unroll
   for (int g = 0; g < 8; ++g)
     if (g < NG) {
-      atomicAdd(&bins[g * 2 + 0], s[g]);
-      atomicAdd(&bins[g * 2 + 1], ss[g]);
+      atomicAdd(&wbins[g * 2 + 0], s[g]);
+      atomicAdd(&wbins[g * 2 + 1], ss[g]);
     }
   __syncthreads();
   // scratch layout: (B*G*2 rows, gridX*chunks*B cols); rows not covered
@@ -159,8 +163,12 @@ __global__ __launch_bounds__(KG_THREADS) void kg_fwd_reduce_kernel(
     const int row_g = (i % (G * 2)) / 2;
     const int half = i & 1;
     float v = 0.f;
-    if (row_b == b && row_g >= g0 && row_g < g0 + NG)
-      v = bins[(row_g - g0) * 2 + half];
+    if (row_b == b && row_g >= g0 && row_g < g0 + NG) {
+      const int k = (row_g - g0) * 2 + half;
+      v = bins[k];
+#pragma unroll
+      for (int w = 1; w < NW; ++w) v += bins[w * 16 + k];
+    }
     scratch[(long)i * cols + col] = v;
   }
 }
@@ -189,9 +197,11 @@ __global__ __launch_bounds__(KG_THREADS) void kg_bwd_reduce_kernel(
   const bool active = p_l < ppb;
   const int n_out = B * G * 2 + C * 2 + 1;
 
-  extern __shared__ float sbins[];
-  for (unsigned i = threadIdx.x; i < (unsigned)n_out; i += KG_THREADS)
-    sbins[i] = 0.f;
+  extern __shared__ float sbins_all[];  // per wave (see the forward reduce)
+  constexpr int NW = KG_THREADS / WAVE;
+  for (unsigned i = threadIdx.x; i < (unsigned)(n_out * NW); i += KG_THREADS)
+    sbins_all[i] = 0.f;
+  float *sbins = sbins_all + wave_id() * n_out;
   __syncthreads();
 
   float sum_dx[4] = {}, sum_dxx[4] = {}, c_dg[4] = {}, c_db[4] = {};
@@ -240,8 +250,12 @@ __global__ __launch_bounds__(KG_THREADS) void kg_bwd_reduce_kernel(
   __syncthreads();
   const long col = (long)blockIdx.x * B + b;
   const long stride = (long)gridDim.x * B;
-  for (unsigned i = threadIdx.x; i < (unsigned)n_out; i += KG_THREADS)
-    scratch[i * stride + col] = sbins[i];
+  for (unsigned i = threadIdx.x; i < (unsigned)n_out; i += KG_THREADS) {
+    float v = sbins_all[i];
+#pragma unroll
+    for (int w = 1; w < NW; ++w) v += sbins_all[w * n_out + i];
+    scratch[i * stride + col] = v;
+  }
 }
 
 // pass 2: d_raw partials per channel chunk + dW / dcb partials.
@@ -402,7 +416,7 @@ void launch_kg_fwd(const float *raw, const float *W, const float *cb,
                    void *y, unsigned char *am, float *vsel,
                    int B, long N, int K, int C, int G, float eps,
                    const float *slope_ptr, bool bf16, int nblk,
-                   hipStream_t stream) {
+                   bool channel_major, hipStream_t stream) {
   const int chunks = C / 4;
   const dim3 grid(nblk, chunks, B);
   hipLaunchKernelGGL(kg_fwd_reduce_kernel<4>, grid, dim3(KG_THREADS), 0,
@@ -412,8 +426,8 @@ void launch_kg_fwd(const float *raw, const float *W, const float *cb,
   launch_gn_finalize_scratch(scratch, (long)nblk * chunks * B, mean, rstd,
                              (long)(C / G) * K * N, B * G, eps, stream);
   launch_gnmp_pick(vmax, vmin, amax, amin, mean, rstd, gamma, beta, y, am,
-                   vsel, (long)B * N * C, (long)N * C, C, G, 2, 0.f,
-                   slope_ptr, bf16, stream);
+                   vsel, B, N, C, G, 2, 0.f, slope_ptr, bf16, channel_major,
+                   stream);
 }
 
 void launch_kg_bwd(const void *dyT, const float *raw, const float *W,
@@ -431,12 +445,14 @@ void launch_kg_bwd(const void *dyT, const float *raw, const float *W,
     const int n_out = B * G * 2 + C * 2 + 1;
     if (bf16)
       hipLaunchKernelGGL(kg_bwd_reduce_kernel<__hip_bfloat16>, rgrid,
-                         dim3(KG_THREADS), (size_t)n_out * sizeof(float),
+                         dim3(KG_THREADS),
+                         (size_t)n_out * (KG_THREADS / WAVE) * sizeof(float),
                          stream, (const __hip_bfloat16 *)dyT, vsel, mean,
                          rstd, gamma, beta, scratch, N, C, G, slope_ptr);
     else
       hipLaunchKernelGGL(kg_bwd_reduce_kernel<float>, rgrid,
-                         dim3(KG_THREADS), (size_t)n_out * sizeof(float),
+                         dim3(KG_THREADS),
+                         (size_t)n_out * (KG_THREADS / WAVE) * sizeof(float),
                          stream, (const float *)dyT, vsel, mean, rstd,
                          gamma, beta, scratch, N, C, G, slope_ptr);
     const int wpb = KG_THREADS / WAVE;

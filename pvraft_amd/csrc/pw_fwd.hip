@@ -44,9 +44,10 @@ typedef __attribute__((ext_vector_type(4))) float f32x4;
 // still yields >= 2 workgroups per CU.
 
 struct PwFwdPart {
-  const void *w;  // (Co, Ci) bf16 row-major
+  const void *w;  // (Co, Ci) bf16, rows ld elements apart
   const void *x;  // (B, Ci, S) bf16
   int ci;
+  int ld;         // >= ci: a column slice of a wider weight needs no copy
 };
 
 template <int NRF, int TC>
@@ -55,8 +56,8 @@ __global__ __launch_bounds__(PF_THREADS) void pw_fwd_kernel(
     const float *__restrict__ bias,   // (Co) fp32 or null
     const void *__restrict__ addend,  // bf16/fp32 slice base or null
     long addend_bstride, int addend_fp32,
-    __hip_bfloat16 *__restrict__ y,   // (B, Co, S)
-    int Co, long S, int act, int pitch) {
+    __hip_bfloat16 *__restrict__ y,   // (B, Co, S), or (B, S, Co) if pm
+    int Co, long S, int act, int pitch, int pm) {
   constexpr int COL16 = TC / 16;        // column tiles per WG
   constexpr int RFG = 4 / COL16;        // wave groups along rows
   constexpr int NRF_PER = (NRF + RFG - 1) / RFG;  // row frags per wave
@@ -82,6 +83,7 @@ __global__ __launch_bounds__(PF_THREADS) void pw_fwd_kernel(
     // descriptors to scratch (measured 112 B of scratch, ~3x slowdown)
     const PwFwdPart pp = pi == 0 ? p0 : pi == 1 ? p1 : pi == 2 ? p2 : p3;
     const int ci = pp.ci;
+    const int ld = pp.ld;
     const int cip = (ci + 31) & ~31;
     const __hip_bfloat16 *w = (const __hip_bfloat16 *)pp.w;
     const __hip_bfloat16 *x =
@@ -94,12 +96,12 @@ __global__ __launch_bounds__(PF_THREADS) void pw_fwd_kernel(
       bf16x8 v = (bf16x8)(__bf16)0.0f;
       if (r < Co) {
         if (c8 + 8 <= ci) {
-          v = *(const bf16x8 *)(w + (long)r * ci + c8);
+          v = *(const bf16x8 *)(w + (long)r * ld + c8);
         } else {
 #pragma unroll
           for (int e = 0; e < 8; ++e)
             if (c8 + e < ci)
-              ((__bf16 *)&v)[e] = *(const __bf16 *)(w + (long)r * ci + c8 + e);
+              ((__bf16 *)&v)[e] = *(const __bf16 *)(w + (long)r * ld + c8 + e);
         }
       }
       *(bf16x8 *)&s_w[(long)r * pitch + c8] = v;
@@ -134,17 +136,25 @@ __global__ __launch_bounds__(PF_THREADS) void pw_fwd_kernel(
     }
   }
 
-  // epilogue: bias + addend + activation, bf16 store
+  // epilogue: bias + addend + activation, bf16 store.  Each lane holds
+  // four consecutive output channels of one column: channel-major they are
+  // four strided scalar stores, point-major (pm, wave-uniform) one packed
+  // 8-byte store when Co % 4 == 0 (o is a multiple of 4, so the quad is
+  // whole and aligned), per-element otherwise.
   const long sc = s0 + ct * 16 + (lane & 15);
   if (sc >= S) return;
   const int crow = (lane >> 4) * 4;
+  const bool pm_packed = pm && (Co & 3) == 0;
 #pragma unroll
-  for (int rf = 0; rf < NRF_PER; ++rf)
+  for (int rf = 0; rf < NRF_PER; ++rf) {
+    if (rf0 + rf >= NRF) continue;
+    const int o0 = (rf0 + rf) * 16 + crow;
+    __hip_bfloat16 q[4];
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      const int o = (rf0 + rf) * 16 + crow + e;
-      if (rf0 + rf < NRF && o < Co) {
-        float v = acc[rf][e];
+      const int o = o0 + e;
+      float v = acc[rf][e];
+      if (o < Co) {
         if (bias != nullptr) v += bias[o];
         if (addend != nullptr) {
           const long ai = (long)b * addend_bstride + (long)o * S + sc;
@@ -152,19 +162,40 @@ __global__ __launch_bounds__(PF_THREADS) void pw_fwd_kernel(
                            : (float)((const __hip_bfloat16 *)addend)[ai];
         }
         if (act == 1) v = v > 0.f ? v : 0.f;
-        y[((long)b * Co + o) * S + sc] = (__hip_bfloat16)v;
+      }
+      q[e] = (__hip_bfloat16)v;
+    }
+    if (pm_packed) {
+      if (o0 < Co) {
+        uint2 pk;
+        pk.x = (unsigned)__bfloat16_as_ushort(q[0]) |
+               ((unsigned)__bfloat16_as_ushort(q[1]) << 16);
+        pk.y = (unsigned)__bfloat16_as_ushort(q[2]) |
+               ((unsigned)__bfloat16_as_ushort(q[3]) << 16);
+        *(uint2 *)&y[((long)b * S + sc) * Co + o0] = pk;
+      }
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int o = o0 + e;
+        if (o < Co) {
+          if (pm) y[((long)b * S + sc) * Co + o] = q[e];
+          else y[((long)b * Co + o) * S + sc] = q[e];
+        }
       }
     }
+  }
 }
 
 void launch_pw_fwd(const void **ws, const void **xs, const int *cis,
-                   int nparts, const float *bias, const void *addend,
+                   const int *lds, int nparts, const float *bias, const void *addend,
                    long addend_bstride, int addend_fp32, void *y, int B,
-                   int Co, long S, int act, hipStream_t stream) {
+                   int Co, long S, int act, int point_major,
+                   hipStream_t stream) {
   PwFwdPart p[PF_MAXP] = {};
   int cip_max = 32;
   for (int i = 0; i < nparts; ++i) {
-    p[i] = PwFwdPart{ws[i], xs[i], cis[i]};
+    p[i] = PwFwdPart{ws[i], xs[i], cis[i], lds[i]};
     const int cip = (cis[i] + 31) & ~31;
     if (cip > cip_max) cip_max = cip;
   }
@@ -192,7 +223,7 @@ void launch_pw_fwd(const void **ws, const void **xs, const int *cis,
     hipLaunchKernelGGL((pw_fwd_kernel<NRF, TC>), grid, dim3(PF_THREADS),      \
                        shmem, stream, p[0], p[1], p[2], p[3], nparts, bias,   \
                        addend, addend_bstride, addend_fp32,                   \
-                       (__hip_bfloat16 *)y, Co, S, act, pitch);               \
+                       (__hip_bfloat16 *)y, Co, S, act, pitch, point_major);  \
   } while (0)
 #define PF_LAUNCH(NRF)                                                        \
   do {                                                                        \

@@ -47,8 +47,8 @@ typedef __attribute__((ext_vector_type(4))) float f32x4;
 // One 64x64 output tile x one (b, chunk) slice of the reduction.
 __device__ __forceinline__ void pw_wgrad_tile(
     const __hip_bfloat16 *__restrict__ dy, const __hip_bfloat16 *__restrict__ x,
-    float *__restrict__ dw, float *__restrict__ dbias, int Co, int Ci, long S,
-    int schunks, int tile_o, int tile_i, int b, int chunk,
+    float *__restrict__ dw, int ldw, float *__restrict__ dbias, int Co, int Ci,
+    long S, int schunks, int tile_o, int tile_i, int b, int chunk,
     __hip_bfloat16 (*sA)[KB + LDS_PAD], __hip_bfloat16 (*sB)[KB + LDS_PAD]) {
   // chunk bounds KB-aligned so in-range stage loads are whole 16B vectors
   const long per = (((S + schunks - 1) / schunks + KB - 1) / KB) * KB;
@@ -151,7 +151,7 @@ __device__ __forceinline__ void pw_wgrad_tile(
       for (int e = 0; e < 4; ++e) {
         const int o = tile_o + wo + a * 16 + crow + e;
         const int i = tile_i + wi + bb * 16 + ccol;
-        if (o < Co && i < Ci) atomicAdd(&dw[(long)o * Ci + i], acc[a][bb][e]);
+        if (o < Co && i < Ci) atomicAdd(&dw[(long)o * ldw + i], acc[a][bb][e]);
       }
 }
 
@@ -163,7 +163,7 @@ __global__ __launch_bounds__(WG_THREADS) void pw_wgrad_kernel(
   __shared__ __hip_bfloat16 sB[TILE][KB + LDS_PAD];
   const int b = blockIdx.z / schunks;
   const int chunk = blockIdx.z % schunks;
-  pw_wgrad_tile(dy, x, dw, dbias, Co, Ci, S, schunks, blockIdx.x * TILE,
+  pw_wgrad_tile(dy, x, dw, Ci, dbias, Co, Ci, S, schunks, blockIdx.x * TILE,
                 blockIdx.y * TILE, b, chunk, sA, sB);
 }
 
@@ -178,7 +178,7 @@ __global__ __launch_bounds__(WG_THREADS) void pw_wgrad_batched_kernel(
   const int to = (m >> 4) & 0xF;
   const int ti = m & 0xF;
   pw_wgrad_tile((const __hip_bfloat16 *)j.dy, (const __hip_bfloat16 *)j.x,
-                j.dw, j.dbias, j.Co, j.Ci, j.S, j.schunks, to * TILE,
+                j.dw, j.ldw, j.dbias, j.Co, j.Ci, j.S, j.schunks, to * TILE,
                 ti * TILE, bz / j.schunks, bz % j.schunks, sA, sB);
 }
 

@@ -202,6 +202,22 @@ def _cast_cached(t: Tensor, dt) -> Tensor:
     # key by their base parameter + view geometry, so the 8-iteration GRU
     # loop hits instead of re-casting ~40 weights per step.
     ck = getattr(t, "_cast_key", None)
+    if (
+        ck is None
+        and t.dim() == 2
+        and not t.is_contiguous()
+        and t.stride(1) == 1
+        and t._base is not None
+        and t._base.is_contiguous()
+        and t._base.numel() == t.shape[0] * t.stride(0)
+        and t.storage_offset() - t._base.storage_offset() + t.shape[1] <= t.stride(0)
+    ):
+        # column slice W[:, lo:hi] of a parameter: the same slice of the
+        # FULL weight's mirror (one entry, batch-refreshed) -- no copy, no
+        # registry entry of its own; consumers take the row pitch
+        lo = t.storage_offset() - t._base.storage_offset()
+        full = _cast_cached(t._base.view(t.shape[0], t.stride(0)), dt)
+        return full[:, lo : lo + t.shape[1]]
     if ck is None:
         base = t._base if t._base is not None else t
         ck = (id(base), tuple(t.shape), tuple(t.stride()),
@@ -319,15 +335,17 @@ class _PwFused(torch.autograd.Function):
     def forward(ctx, bias, addend, conf, *wx):
         from pvraft_amd import _C
 
-        act_id, targets, p, compute_dt = conf
+        act_id, targets, p, compute_dt = conf[:4]
+        point_major = len(conf) > 4 and conf[4]
         ws = [
             w if compute_dt is None else _cast_cached(w, compute_dt)
             for w in wx[:p]
         ]
         xs = list(wx[p:])
-        y = _C.pw_fwd(ws, xs, bias, addend, act_id)
+        y = _C.pw_fwd(ws, xs, bias, addend, act_id, point_major)
         ctx.save_for_backward(*ws, *xs, y)
         ctx.conf = (act_id, targets, p)
+        ctx.point_major = point_major
         ctx.has_bias = bias is not None
         ctx.has_addend = addend is not None
         ctx.w_dtypes = tuple(w.dtype for w in wx[:p])
@@ -342,6 +360,11 @@ class _PwFused(torch.autograd.Function):
         dpre = (
             torch.ops.aten.threshold_backward(dy, y, 0) if act_id == 1 else dy
         )
+        if ctx.point_major:
+            # (B, S, Co) -> (B, Co, S) once; dx / wgrad proceed as usual
+            from pvraft_amd import _C
+
+            dpre = _C.batched_transpose(dpre)
         d_addend = dpre if ctx.has_addend else None
         dxs = [
             torch.bmm(w.t().unsqueeze(0).expand(dpre.shape[0], -1, -1), dpre)
@@ -359,9 +382,12 @@ class _PwFused(torch.autograd.Function):
                     if i == 0 and need_bias and targets[p] is not None:
                         bt = _grad_buffer(targets[p]).view(-1)
                         need_bias = False
-                    _DEFER.jobs.append(
-                        (dpre, xs[i], _grad_buffer(targets[i]).view(-1), bt)
-                    )
+                    tb = _grad_buffer(targets[i])
+                    # a (Co, Ci) column block of a wider grad buffer stays
+                    # 2-D: the batched kernel takes its row pitch
+                    if tb.is_contiguous():
+                        tb = tb.view(-1)
+                    _DEFER.jobs.append((dpre, xs[i], tb, bt))
         else:
             for i in range(p):
                 if ctx.needs_input_grad[3 + i]:
@@ -381,12 +407,15 @@ class _PwFused(torch.autograd.Function):
         return (d_bias, d_addend, None, *dws, *dxs)
 
 
-def pw_fused(parts, bias=None, bias_target=None, addend=None, act="none") -> Tensor:
+def pw_fused(parts, bias=None, bias_target=None, addend=None, act="none",
+             out_point_major=False) -> Tensor:
     """act(sum_i w_i @ x_i + bias + addend) for 1x1-conv stacks.
 
     parts: list of (w (Co, Ci), x (B, Ci, S), wgrad_target_or_None).
     GPU + bf16 compute: one fused MFMA kernel.  Otherwise: composed
     pw_matmul calls (+ add/activation), same semantics.
+    ``out_point_major``: the result is (B, S, Co) contiguous, stored that
+    way by the kernel's epilogue (no separate transpose).
     """
     import torch.nn.functional as F
 
@@ -420,7 +449,8 @@ def pw_fused(parts, bias=None, bias_target=None, addend=None, act="none") -> Ten
             x.to(dt).contiguous() for _w, x, _t in parts
         )
         b = bias.float() if bias is not None and bias.dtype != torch.float32 else bias
-        return _PwFused.apply(b, addend, (act_id, targets, p, dt), *wx)
+        return _PwFused.apply(
+            b, addend, (act_id, targets, p, dt, bool(out_point_major)), *wx)
     out = None
     for i, (w, x, tgt) in enumerate(parts):
         b = bias if i == 0 else None
@@ -431,6 +461,10 @@ def pw_fused(parts, bias=None, bias_target=None, addend=None, act="none") -> Ten
         out = out + addend
     if act == "relu":
         out = F.relu(out)
+    if out_point_major:
+        from pvraft_amd import ops
+
+        out = ops.transpose_last2(out)
     return out
 
 

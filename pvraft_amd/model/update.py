@@ -251,7 +251,11 @@ class FlowHead(nn.Module):
         from pvraft_amd import ops
 
         out = self.conv1(x)
-        out_set = ops.transpose_last2(self.setconv(ops.transpose_last2(x), graph))
+        if ops.channel_major_layout():
+            # SetConv's channel-major entry: net is never transposed
+            out_set = self.setconv.forward_cn(x, graph)
+        else:
+            out_set = ops.transpose_last2(self.setconv(ops.transpose_last2(x), graph))
         # out_conv(cat([out_set, out])) without the cat; ReLU fused
         wp = wcache.get("flowhead") if wcache else None
         mid = _split_mm(self.out_conv[0].weight, self.out_conv[0].bias,

@@ -90,6 +90,13 @@ def hip_available() -> bool:
     return _load_ext() is not None
 
 
+def channel_major_layout() -> bool:
+    """SetConv stage 1 / kNN-branch head write their pooled output
+    channel-major straight from the kernels; PVRAFT_SETCONV_LAYOUT=classic
+    restores the point-major output + separate transpose composition."""
+    return os.environ.get("PVRAFT_SETCONV_LAYOUT", "fused") != "classic"
+
+
 # ---------------------------------------------------------------------------
 # autograd wrappers around the HIP kernels
 # ---------------------------------------------------------------------------
@@ -328,13 +335,16 @@ class _EdgeGNMP(torch.autograd.Function):
     deterministic CSR walk."""
 
     @staticmethod
-    def forward(ctx, wg_t, idx, offsets, order_n, order_j, num_groups, weight, bias, eps, act, slope, slope_t):
+    def forward(ctx, wg_t, idx, offsets, order_n, order_j, num_groups, weight, bias, eps, act, slope, slope_t,
+                channel_major_out=False):
         w = weight.float().contiguous()
         b = bias.float().contiguous()
         st_ = slope_t.float().reshape(1).contiguous() if slope_t is not None else None
-        y, am, vsel, vsum, mean, rstd = _EXT.edge_gnmp_fwd(wg_t, idx, num_groups, w, b, eps, act, slope, st_)
+        y, am, vsel, vsum, mean, rstd = _EXT.edge_gnmp_fwd(
+            wg_t, idx, num_groups, w, b, eps, act, slope, st_, channel_major_out)
         ctx.save_for_backward(wg_t, idx, am, vsel, vsum, offsets, order_n, order_j, mean, rstd, w, b, st_)
         ctx.conf = (num_groups, act, slope, weight.dtype)
+        ctx.channel_major_out = channel_major_out
         ctx.params = (weight, bias, slope_t)
         return y
 
@@ -343,6 +353,11 @@ class _EdgeGNMP(torch.autograd.Function):
         (wg_t, idx, am, vsel, vsum, offsets, order_n, order_j, mean, rstd,
          w, b, st_) = ctx.saved_tensors
         num_groups, act, slope, wdtype = ctx.conf
+        dy = dy.contiguous()
+        if ctx.channel_major_out:
+            # the backward kernels read dy point-major: one transpose, as
+            # the autograd of the caller's output transpose did before
+            dy = _EXT.batched_transpose(dy)
         tgt = _gn_defer_targets(*ctx.params, act)
         if tgt is not None:
             (dwg,) = _EXT.edge_gnmp_bwd(
@@ -352,7 +367,7 @@ class _EdgeGNMP(torch.autograd.Function):
                 tgt[0], tgt[1], tgt[2],
             )
             return (dwg, None, None, None, None, None, None, None, None,
-                    None, None, None)
+                    None, None, None, None)
         dwg, dw, db, dsl = _EXT.edge_gnmp_bwd(
             dy.contiguous(), wg_t, idx, am, vsel, vsum, offsets, order_n,
             order_j,
@@ -360,7 +375,7 @@ class _EdgeGNMP(torch.autograd.Function):
         )
         dslope = dsl.to(wdtype) if act == 2 else None
         return (dwg, None, None, None, None, None, dw.to(wdtype),
-                db.to(wdtype), None, None, None, dslope)
+                db.to(wdtype), None, None, None, dslope, None)
 
 
 def edge_gnmp(
@@ -374,16 +389,18 @@ def edge_gnmp(
     act: str = "lrelu",
     slope: float = 0.1,
     slope_t: Optional[Tensor] = None,
+    channel_major_out: bool = False,
 ) -> Tensor:
     """(B, N, M) wg + (B, N, K) neighbours -> (B, N, M) pooled SetConv
-    stage 1 (gather-diff -> GN -> act -> max over K), GPU only."""
+    stage 1 (gather-diff -> GN -> act -> max over K), GPU only.
+    ``channel_major_out``: the pooled result is written (B, M, N)."""
     if not _use_hip(wg_t):
         raise RuntimeError("edge_gnmp is a GPU-only fused op")
     act_id = {"none": 0, "lrelu": 1, "prelu": 2}[act]
     _order, offsets, order_n, order_j = csr
     return _EdgeGNMP.apply(
         wg_t.contiguous(), idx, offsets, order_n, order_j, num_groups,
-        weight, bias, eps, act_id, slope, slope_t,
+        weight, bias, eps, act_id, slope, slope_t, channel_major_out,
     )
 
 
@@ -394,7 +411,8 @@ class _KnnGNMP(torch.autograd.Function):
     autocast dtype."""
 
     @staticmethod
-    def forward(ctx, raw, weight, cbias, num_groups, gamma, beta, eps, slope_t):
+    def forward(ctx, raw, weight, cbias, num_groups, gamma, beta, eps, slope_t,
+                channel_major_out=False):
         w = weight.view(weight.shape[0], 4).float().contiguous()
         cb = cbias.float().contiguous()
         ga = gamma.float().contiguous()
@@ -403,9 +421,11 @@ class _KnnGNMP(torch.autograd.Function):
         out_bf16 = raw.is_cuda and torch.is_autocast_enabled() and (
             torch.get_autocast_dtype("cuda") == torch.bfloat16)
         y, am, vsel, mean, rstd = _EXT.knn_gnmp_fwd(
-            raw, w, cb, num_groups, ga, be, eps, st, out_bf16)
+            raw, w, cb, num_groups, ga, be, eps, st, out_bf16,
+            channel_major_out)
         ctx.save_for_backward(raw, w, cb, am, vsel, mean, rstd, ga, be, st)
         ctx.conf = (num_groups, weight.shape, weight.dtype)
+        ctx.channel_major_out = channel_major_out
         ctx.param_refs = (weight, cbias, gamma, beta, slope_t)
         return y
 
@@ -415,8 +435,11 @@ class _KnnGNMP(torch.autograd.Function):
 
         raw, w, cb, am, vsel, mean, rstd, ga, be, st = ctx.saved_tensors
         num_groups, wshape, wdtype = ctx.conf
+        dy = dy.contiguous()
+        if ctx.channel_major_out:
+            dy = _EXT.batched_transpose(dy)  # kernels read dy point-major
         draw, dW, dcb, dgamma, dbeta, dslope = _EXT.knn_gnmp_bwd(
-            dy.contiguous(), raw, w, cb, am, vsel, mean, rstd, num_groups,
+            dy, raw, w, cb, am, vsel, mean, rstd, num_groups,
             ga, be, st)
         params = ctx.param_refs
         if pointwise._DEFER.on and all(
@@ -435,17 +458,24 @@ class _KnnGNMP(torch.autograd.Function):
             pointwise._grad_buffer(gat).add_(dgamma)
             pointwise._grad_buffer(bet).add_(dbeta)
             pointwise._grad_buffer(slt).view(-1).add_(dslope)
-            return (draw, None, None, None, None, None, None, None)
+            return (draw, None, None, None, None, None, None, None, None)
         return (draw, dW.view(wshape).to(wdtype), dcb, None, dgamma, dbeta,
-                None, dslope.reshape(1))
+                None, dslope.reshape(1), None)
 
 
 def knn_gnmp(raw: Tensor, weight: Tensor, cbias: Tensor, num_groups: int,
-             gamma: Tensor, beta: Tensor, eps: float, slope_t: Tensor) -> Tensor:
+             gamma: Tensor, beta: Tensor, eps: float, slope_t: Tensor,
+             channel_major_out: Optional[bool] = None) -> Tensor:
     """raw (B, 4, K, N) fp32 -> (B, C, N): conv -> GN -> PReLU -> max over
     K in one fused pipeline, GPU only."""
     if not _use_hip(raw):
         raise RuntimeError("knn_gnmp is a GPU-only fused op")
+    if channel_major_out is None:
+        channel_major_out = channel_major_layout()
+    if channel_major_out:
+        # the pick kernel writes (B, C, N) itself
+        return _KnnGNMP.apply(raw.contiguous(), weight, cbias, num_groups,
+                              gamma, beta, eps, slope_t, True)
     y = _KnnGNMP.apply(raw.contiguous(), weight, cbias, num_groups, gamma,
                        beta, eps, slope_t)
     return transpose_last2(y)  # (B, N, C) -> (B, C, N), narrow-R fast path
@@ -487,12 +517,27 @@ def morton_order(xyz: Tensor, need_inv: bool = True):
     return perm, inv
 
 
-def knn_graph(xyz: Tensor, k: int) -> Tensor:
-    """(B,N,3) -> (B,N,k) int64 neighbour indices (self included)."""
+def knn_graph_pair(xyz: Tensor, k: int) -> Tuple[Tensor, Optional[Tensor]]:
+    """(B,N,3) -> ((B,N,k) int64 neighbour indices, the kernel's own int32
+    result or None on the reference backend)."""
     xyz = xyz.contiguous().float()
     if _use_hip(xyz):
-        return _EXT.knn_graph(xyz, k).long()
-    return reference.knn_idx(xyz, k)
+        idx32 = _EXT.knn_graph(xyz, k)
+        return idx32.long(), idx32
+    return reference.knn_idx(xyz, k), None
+
+
+def knn_graph(xyz: Tensor, k: int) -> Tensor:
+    """(B,N,3) -> (B,N,k) int64 neighbour indices (self included)."""
+    return knn_graph_pair(xyz, k)[0]
+
+
+def knn_csr(idx32: Tensor) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """(B,N,k) int32 -> inverse adjacency (order, offsets, order_n, order_j),
+    edge ids j*N+n sorted by (target, id) (csrc/knn_csr.hip)."""
+    if _load_ext() is None:
+        raise RuntimeError(f"pvraft_amd._C is not built: {_EXT_ERR}")
+    return tuple(_EXT.knn_csr(idx32.contiguous()))
 
 
 class _KnnInterpolate(torch.autograd.Function):

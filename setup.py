@@ -16,6 +16,7 @@ from torch.utils.cpp_extension import BuildExtension, CUDAExtension
 SOURCES = [
     "pvraft_amd/csrc/bindings.cpp",
     "pvraft_amd/csrc/knn_graph.hip",
+    "pvraft_amd/csrc/knn_csr.hip",
     "pvraft_amd/csrc/knn_interp.hip",
     "pvraft_amd/csrc/gather_edge.hip",
     "pvraft_amd/csrc/voxel_corr.hip",
