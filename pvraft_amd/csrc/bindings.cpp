@@ -23,6 +23,10 @@ void launch_flow_smooth_bwd(const float*, const int*, const int*, const int*,
                             const float*, float*, int, int, int, int,
                             hipStream_t);
 int flow_smooth_blocks(int);
+void launch_rigid_fit(const float*, const float*, const float*, float*, float*,
+                      float*, unsigned char*, int, int, float, int,
+                      hipStream_t);
+int rigid_fit_reg_points();
 void launch_morton_keys(const float*, const float*, const float*, long*,
                         int, long, hipStream_t);
 void launch_gather_edge_fwd(const void*, const int*, const float*, void*,
@@ -1388,7 +1392,47 @@ torch::Tensor flow_smooth_bwd(torch::Tensor flows, torch::Tensor idx,
   return dflow;
 }
 
+// src (B,N,3), dst (B,N,3) f32, optional prior weights (B,N) f32 ->
+// {R (B,3,3) f32, t (B,3) f32, residual (B,N) f32, ok (B) bool}: weighted
+// Kabsch fit inside `iters` rounds of Cauchy reweighting, one launch, no
+// host synchronisation
+std::vector<torch::Tensor> rigid_fit(torch::Tensor src, torch::Tensor dst,
+                                     c10::optional<torch::Tensor> weights,
+                                     double thresh, int64_t iters) {
+  check_f32(src, "src");
+  check_f32(dst, "dst");
+  TORCH_CHECK(src.dim() == 3 && src.size(2) == 3, "src must be (B,N,3)");
+  TORCH_CHECK(dst.sizes() == src.sizes() && dst.device() == src.device(),
+              "dst must match src in shape and device");
+  const int64_t B = src.size(0), N = src.size(1);
+  TORCH_CHECK(B >= 1 && N >= 1, "rigid_fit requires B, N >= 1");
+  TORCH_CHECK(N < (1L << 30), "rigid_fit sizes exceed 32-bit point indexing");
+  TORCH_CHECK(iters >= 0 && iters <= 64, "rigid_fit requires 0 <= iters <= 64");
+  TORCH_CHECK(thresh > 0.0, "rigid_fit requires thresh > 0");
+  const float* wp = nullptr;
+  if (weights.has_value()) {
+    const torch::Tensor& w = *weights;
+    check_f32(w, "weights");
+    TORCH_CHECK(w.dim() == 2 && w.size(0) == B && w.size(1) == N &&
+                    w.device() == src.device(),
+                "weights must be (B,N) on the device of src");
+    wp = w.data_ptr<float>();
+  }
+  auto R = torch::empty({B, 3, 3}, src.options());
+  auto t = torch::empty({B, 3}, src.options());
+  auto res = torch::empty({B, N}, src.options());
+  auto ok = torch::empty({B}, src.options().dtype(torch::kBool));
+  launch_rigid_fit(src.data_ptr<float>(), dst.data_ptr<float>(), wp,
+                   R.data_ptr<float>(), t.data_ptr<float>(),
+                   res.data_ptr<float>(),
+                   reinterpret_cast<unsigned char*>(ok.data_ptr<bool>()), (int)B,
+                   (int)N, (float)thresh, (int)iters, stream());
+  return {R, t, res, ok};
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  m.def("rigid_fit", &rigid_fit);
+  m.attr("RIGID_FIT_REG_POINTS") = rigid_fit_reg_points();
   m.def("chamfer_fwd", &chamfer_fwd);
   m.def("chamfer_nn_fwd", &chamfer_nn_fwd);
   m.def("chamfer_bwd", &chamfer_bwd);

@@ -14,6 +14,14 @@ interpolates the final flow from the sampled pc1 onto the full-resolution
 cloud (ops.knn_interpolate, --dense_k neighbours) and reports dense_*
 metrics over every masked point; the sparse path and its metrics are
 untouched.
+
+--ego_motion (also beyond the reference) fits the rigid motion that explains
+the static part of the predicted flow (ops.ego_motion, --ego_thresh,
+--ego_iters) and the same for the ground-truth flow with the ground-truth
+mask as prior weights -- the dataset's own ego-motion.  It reports the
+rotation / translation error between the two fits, the share of points
+classified static, and rigid_* metrics of the flow whose static points are
+snapped onto the fitted motion.
 """
 
 from __future__ import annotations
@@ -58,9 +66,12 @@ def evaluate(args):
     dataset = build_eval_dataset(args)
     dense = bool(getattr(args, "dense", False))
     dense_k = int(getattr(args, "dense_k", 3))
-    if dense:
+    ego = bool(getattr(args, "ego_motion", False))
+    ego_thresh = float(getattr(args, "ego_thresh", 0.05))
+    ego_iters = int(getattr(args, "ego_iters", 10))
+    if dense or ego:
         from pvraft_amd import ops
-
+    if dense:
         dataset.return_full = True
     loader = DataLoader(
         dataset,
@@ -90,6 +101,7 @@ def evaluate(args):
                               amp=bool(getattr(args, "amp", False)))
     sums = [0.0] * 5
     dense_sums = [0.0] * 4
+    ego_sums = [0.0] * 7
     n = 0
     for batch in loader:
         batch = batch.to(device, non_blocking=True)
@@ -121,6 +133,20 @@ def evaluate(args):
             dense_m = compute_epe(flow_dense, {"ground_truth": [mask_full, flow_full]})
             for j, v in enumerate(dense_m):
                 dense_sums[j] += v
+        if ego:
+            pc1 = batch["sequence"][0].float()
+            gt_mask, gt_flow = batch["ground_truth"]
+            fit = ops.ego_motion(pc1, final.float(), thresh=ego_thresh, iters=ego_iters)
+            gt_fit = ops.ego_motion(pc1, gt_flow.float(), thresh=ego_thresh, iters=ego_iters,
+                                    weights=gt_mask[..., 0].float())
+            rel = fit.R @ gt_fit.R.transpose(1, 2)
+            cos = ((rel.diagonal(dim1=1, dim2=2).sum(-1) - 1) / 2).clamp(-1, 1)
+            rot_err = torch.rad2deg(torch.acos(cos)).mean().item()
+            trans_err = (fit.t - gt_fit.t).norm(dim=-1).mean().item()
+            flow_rigid = torch.where(fit.static.unsqueeze(-1), fit.rigid_flow, final.float())
+            rigid_m = compute_epe(flow_rigid, batch)
+            for j, v in enumerate((rot_err, trans_err, fit.static.float().mean().item()) + tuple(rigid_m)):
+                ego_sums[j] += v
         if dump:
             import numpy as np
 
@@ -132,6 +158,11 @@ def evaluate(args):
             if dense:
                 np.save(os.path.join(d, "pc1_full.npy"), pc1_full.cpu().numpy())
                 np.save(os.path.join(d, "flow_dense.npy"), flow_dense.cpu().numpy())
+            if ego:
+                np.save(os.path.join(d, "ego_R.npy"), fit.R.cpu().numpy())
+                np.save(os.path.join(d, "ego_t.npy"), fit.t.cpu().numpy())
+                np.save(os.path.join(d, "static_mask.npy"), fit.static.cpu().numpy())
+                np.save(os.path.join(d, "flow_rigid.npy"), flow_rigid.cpu().numpy())
         n += 1
     means = [s / max(n, 1) for s in sums]
     log.info(
@@ -156,5 +187,22 @@ def evaluate(args):
             dense_acc3d_strict=dmeans[1],
             dense_acc3d_relax=dmeans[2],
             dense_outlier=dmeans[3],
+        )
+    if ego:
+        emeans = [s / max(n, 1) for s in ego_sums]
+        log.info(
+            f"[test {args.dataset} ego thresh={ego_thresh} iters={ego_iters}] "
+            f"rot_err={emeans[0]:.4f}deg trans_err={emeans[1]:.4f} static={emeans[2]:.4f} "
+            f"rigid EPE3D={emeans[3]:.4f} Acc3DS={emeans[4]:.4f} Acc3DR={emeans[5]:.4f} "
+            f"Outlier={emeans[6]:.4f}"
+        )
+        results.update(
+            ego_rot_err_deg=emeans[0],
+            ego_trans_err=emeans[1],
+            ego_static_ratio=emeans[2],
+            rigid_epe=emeans[3],
+            rigid_acc3d_strict=emeans[4],
+            rigid_acc3d_relax=emeans[5],
+            rigid_outlier=emeans[6],
         )
     return results

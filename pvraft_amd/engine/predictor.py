@@ -10,6 +10,9 @@ launch-collapse as the training step, applied to serving.
 
     # flow for every point of full-resolution clouds (batch-1 predictors):
     dense = pred.predict_dense(pc1_full, pc2_full, k=3)   # (n1, 3)
+
+    # flow plus the ego-motion it implies and a static/dynamic split:
+    flow, ego = pred.predict_ego_motion(xyz1, xyz2)       # ego.R, ego.t, ...
 """
 
 from __future__ import annotations
@@ -82,6 +85,19 @@ class Predictor:
         self._graph.replay()
         self.last_flows = self._flows
         return self._flows[-1].clone()
+
+    @torch.no_grad()
+    def predict_ego_motion(self, xyz1: torch.Tensor, xyz2: torch.Tensor,
+                           thresh: float = 0.05, iters: int = 10):
+        """(flow (B,N,3), ``ops.EgoMotion``): the usual forward (graph
+        replay as in ``__call__``), then the robust rigid fit of the final
+        flow -- one fused launch, run eagerly after the replay without
+        draining the stream.  Works for any predictor batch."""
+        from pvraft_amd import ops
+
+        flow = self(xyz1, xyz2)
+        ego = ops.ego_motion(xyz1.to(self.device).float(), flow, thresh=thresh, iters=iters)
+        return flow, ego
 
     @torch.no_grad()
     def predict_dense(self, pc1_full: torch.Tensor, pc2_full: torch.Tensor, k: int = 3,

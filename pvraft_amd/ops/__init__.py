@@ -17,7 +17,7 @@ from __future__ import annotations
 
 import math
 import os
-from typing import Optional, Tuple
+from typing import NamedTuple, Optional, Tuple
 
 import torch
 from torch import Tensor
@@ -990,3 +990,92 @@ def flow_smoothness(flows, graph) -> Tensor:
     if flows.dtype != torch.float64:
         flows = flows.float()
     return reference.flow_smoothness(flows.contiguous(), graph.idx)
+
+
+# ---------------------------------------------------------------------------
+# ego-motion from scene flow (csrc/rigid_fit.hip)
+# ---------------------------------------------------------------------------
+
+
+class EgoMotion(NamedTuple):
+    """Result of ``ego_motion``: R (B,3,3), t (B,3), residual (B,N), static
+    (B,N) bool, rigid_flow (B,N,3), ok (B,) bool."""
+
+    R: Tensor
+    t: Tensor
+    residual: Tensor
+    static: Tensor
+    rigid_flow: Tensor
+    ok: Tensor
+
+
+def rigid_fit(
+    src: Tensor, dst: Tensor, weights: Optional[Tensor] = None, thresh: float = 0.05, iters: int = 0
+) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """Robust rigid transform between two corresponding clouds: src (B,N,3),
+    dst (B,N,3), optional prior weights (B,N) -> R (B,3,3), t (B,3),
+    residual (B,N), ok (B,) bool, 0 <= iters <= 64, thresh > 0,
+
+      w0_i = weights_i (1 without weights)
+      for k = 0 .. iters:
+          (R, t) = argmin sum_i w_i |R src_i + t - dst_i|^2,  det R = +1
+          r_i    = |R src_i + t - dst_i|
+          if k < iters:  w_i = w0_i / (1 + (r_i / thresh)^2)    (Cauchy)
+
+    so ``iters=0`` is the plain weighted Kabsch fit.  ``residual`` belongs
+    to the last fit.  A point with a non-finite coordinate is skipped and
+    reports residual +INF; a point with a non-finite weight or a weight <= 0
+    is skipped but still gets its residual.  ``ok`` is False when fewer than
+    3 points carry positive weight or a sum is non-finite: then R = I and t
+    is the w0-weighted mean of dst - src (0 when no point is usable); a
+    cloud of fewer than 3 points is not an error.  Planar clouds get the
+    proper rotation (never a reflection); for collinear clouds R is one of
+    the minimisers.
+
+    GPU: one fused launch for the whole loop (one workgroup per batch
+    element, no host synchronisation), bit-reproducible run to run.
+    Not differentiable: the outputs are detached.  bf16/fp16 or
+    non-contiguous inputs are upcast / made contiguous here.
+    """
+    if not 0 <= int(iters) <= 64:
+        raise ValueError(f"rigid_fit requires 0 <= iters <= 64, got {iters}")
+    if not float(thresh) > 0:
+        raise ValueError(f"rigid_fit requires thresh > 0, got {thresh}")
+    if src.dim() != 3 or src.shape[-1] != 3 or dst.shape != src.shape:
+        raise ValueError(f"rigid_fit needs src, dst (B,N,3), got {tuple(src.shape)}, {tuple(dst.shape)}")
+    if weights is not None and weights.shape != src.shape[:2]:
+        raise ValueError(f"rigid_fit needs weights (B,N), got {tuple(weights.shape)}")
+    if _use_hip(src):
+        w = None if weights is None else weights.detach().float().contiguous()
+        R, t, res, ok = _EXT.rigid_fit(
+            src.detach().float().contiguous(), dst.detach().float().contiguous(), w, float(thresh), int(iters)
+        )
+        return R, t, res, ok
+    if weights is None:
+        src, dst = _fp32_unless_all_fp64(src.detach(), dst.detach())
+    else:
+        src, dst, weights = _fp32_unless_all_fp64(src.detach(), dst.detach(), weights.detach())
+    return reference.rigid_fit(src.contiguous(), dst.contiguous(), weights, float(thresh), int(iters))
+
+
+def ego_motion(
+    pc1: Tensor, flow: Tensor, thresh: float = 0.05, iters: int = 10, weights: Optional[Tensor] = None
+) -> EgoMotion:
+    """Ego-motion explained by a flow field: pc1 (B,N,3), flow (B,N,3) ->
+    ``EgoMotion(R, t, residual, static, rigid_flow, ok)``.
+
+    (R, t, residual, ok) = ``rigid_fit(pc1, pc1 + flow, weights, thresh,
+    iters)``: the rigid motion of the static part of the scene, robust to
+    independently moving points.  ``static`` (B,N) bool marks the points
+    whose flow agrees with it (residual < thresh; never a point with a
+    non-finite coordinate) and ``rigid_flow = pc1 @ R^T + t - pc1`` (B,N,3)
+    is the flow that motion alone induces at every point.  Not
+    differentiable; deterministic.
+    """
+    pc1 = pc1.detach()
+    flow = flow.detach()
+    R, t, residual, ok = rigid_fit(pc1, pc1 + flow, weights, thresh, iters)
+    static = residual < thresh
+    p = pc1.to(R.dtype)
+    rigid_flow = p @ R.transpose(1, 2) + t.unsqueeze(1) - p
+    return EgoMotion(R, t, residual, static, rigid_flow, ok)

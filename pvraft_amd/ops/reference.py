@@ -20,7 +20,7 @@ query rows, which is also the shape the HIP kernels use (tiled, streaming).
 from __future__ import annotations
 
 import math
-from typing import Tuple
+from typing import Optional, Tuple
 
 import torch
 from torch import Tensor
@@ -319,3 +319,88 @@ def flow_smoothness(flows, idx: Tensor) -> Tensor:
     nb = flows.gather(2, flat).view(T, B, N, k, 3)
     d = nb - flows.unsqueeze(3)
     return (d * d).sum(-1).mean(dim=(1, 2, 3))
+
+
+# ---------------------------------------------------------------------------
+# Ego-motion (absent in the reference): robust rigid fit of a flow field
+# ---------------------------------------------------------------------------
+
+
+def rigid_fit(
+    src: Tensor, dst: Tensor, weights: Optional[Tensor] = None, thresh: float = 0.05, iters: int = 0
+) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """Weighted Kabsch fit inside ``iters`` rounds of Cauchy reweighting:
+    src (B,N,3), dst (B,N,3), weights (B,N) or None -> R (B,3,3), t (B,3),
+    residual (B,N), ok (B,) bool, in the dtype of ``src``.
+
+      w0_i = weights_i (1 without weights; 0 for a point with a non-finite
+             coordinate, a non-finite weight or a weight <= 0)
+      for k = 0 .. iters:
+          (R, t) = argmin sum_i w_i |R src_i + t - dst_i|^2,  det R = +1
+          r_i    = |R src_i + t - dst_i|
+          if k < iters:  w_i = w0_i / (1 + (r_i / thresh)^2)
+
+    ``residual`` belongs to the last fit (+INF where a coordinate is
+    non-finite).  ``ok`` is False when fewer than 3 points carry positive
+    weight or a sum is non-finite; then R = I and t is the w0-weighted mean
+    of dst - src (0 when no point is usable).  The rotation comes from
+    ``torch.linalg.svd`` of the centred cross-covariance with the
+    determinant sign fix.  Not differentiable.
+    """
+    if not 0 <= int(iters) <= 64:
+        raise ValueError(f"rigid_fit requires 0 <= iters <= 64, got {iters}")
+    if not float(thresh) > 0:
+        raise ValueError(f"rigid_fit requires thresh > 0, got {thresh}")
+    with torch.no_grad():
+        B, N, _ = src.shape
+        dt, dev = src.dtype, src.device
+        d = dst - src
+        fin = torch.isfinite(src).all(-1) & torch.isfinite(dst).all(-1) & torch.isfinite(d).all(-1)
+        prior = torch.ones(B, N, dtype=dt, device=dev) if weights is None else weights.to(dt)
+        zero = torch.zeros((), dtype=dt, device=dev)
+        w0 = torch.where(fin & torch.isfinite(prior) & (prior > 0), prior, zero)
+        p = torch.where(fin.unsqueeze(-1), src, zero)
+        d = torch.where(fin.unsqueeze(-1), d, zero)
+        use = (w0 > 0).to(dt)
+        n_use = use.sum(1)
+        # pivot: unweighted mean of the usable points
+        c = (p * use.unsqueeze(-1)).sum(1) / n_use.clamp_min(1).unsqueeze(-1)
+        c = torch.where(torch.isfinite(c), c, zero)
+        pc = p - c.unsqueeze(1)
+
+        eye = torch.eye(3, dtype=dt, device=dev).expand(B, 3, 3)
+        ok = torch.ones(B, dtype=torch.bool, device=dev)
+        tfall = torch.zeros(B, 3, dtype=dt, device=dev)
+        w = w0
+        for k in range(int(iters) + 1):
+            sw = w.sum(1)
+            safe = sw.clamp_min(torch.finfo(dt).tiny).unsqueeze(-1)
+            pm = (w.unsqueeze(-1) * pc).sum(1) / safe
+            dm = (w.unsqueeze(-1) * d).sum(1) / safe
+            pt = pc - pm.unsqueeze(1)
+            qt = pt + (d - dm.unsqueeze(1))
+            H = torch.einsum("bn,bni,bnj->bij", w, pt, qt)
+            finite = (
+                torch.isfinite(sw) & torch.isfinite(pm).all(-1) & torch.isfinite(dm).all(-1)
+                & torch.isfinite(H).all(-1).all(-1)
+            )
+            have = finite & (sw > 0)
+            if k == 0:
+                tfall = torch.where(have.unsqueeze(-1), dm, tfall)
+            ok = ok & have & (n_use >= 3)
+            U, _, Vh = torch.linalg.svd(torch.where(ok.view(B, 1, 1), H, eye))
+            V = Vh.transpose(1, 2)
+            sign = torch.where(torch.linalg.det(V @ U.transpose(1, 2)) < 0, -1.0, 1.0).to(dt)
+            D = torch.diag_embed(torch.stack([torch.ones_like(sign), torch.ones_like(sign), sign], -1))
+            R = V @ D @ U.transpose(1, 2)
+            E = torch.where(ok.view(B, 1, 1), R - eye, torch.zeros_like(R))
+            tp = torch.where(ok.unsqueeze(-1), dm - (E @ pm.unsqueeze(-1)).squeeze(-1), tfall)
+            e = pc @ E.transpose(1, 2) + tp.unsqueeze(1) - d
+            r = e.norm(dim=-1)
+            if k < iters:
+                w = w0 / (1 + (r / thresh) ** 2)
+                w = torch.where(w > 0, w, zero)  # drops NaN / overflowed residuals
+        R = E + eye
+        t = tp - (E @ c.unsqueeze(-1)).squeeze(-1)
+        r = torch.where(fin, r, torch.full_like(r, float("inf")))
+        return R.contiguous(), t, r, ok

@@ -35,6 +35,7 @@ SOURCES = [
     "pvraft_amd/csrc/seq_loss.hip",
     "pvraft_amd/csrc/chamfer.hip",
     "pvraft_amd/csrc/flow_smooth.hip",
+    "pvraft_amd/csrc/rigid_fit.hip",
 ]
 
 setup(

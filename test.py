@@ -20,6 +20,9 @@ def parse_args():
     parser.add_argument("--dump_results", help="write result/<dataset>/<i>/{pc1,pc2,flow}.npy for visual.py", action="store_true")
     parser.add_argument("--dense", help="also interpolate the flow onto the full-resolution pc1 and report dense_* metrics", action="store_true")
     parser.add_argument("--dense_k", help="neighbours for the dense interpolation", default=3, type=int)
+    parser.add_argument("--ego_motion", help="also fit the ego-motion of the predicted flow and report ego_* / rigid_* metrics", action="store_true")
+    parser.add_argument("--ego_thresh", help="static/dynamic residual threshold of the ego-motion fit (m)", default=0.05, type=float)
+    parser.add_argument("--ego_iters", help="reweighting rounds of the ego-motion fit", default=10, type=int)
     return parser.parse_args()
 
 
