@@ -27,6 +27,15 @@ void launch_rigid_fit(const float*, const float*, const float*, float*, float*,
                       float*, unsigned char*, int, int, float, int,
                       hipStream_t);
 int rigid_fit_reg_points();
+void launch_segmented_rigid_fit(const float*, const float*, const float*,
+                                const int*, float*, float*, float*,
+                                unsigned char*, int, int, int, float, int,
+                                hipStream_t);
+int segmented_fit_capacity();
+void launch_cluster_points(const float*, const float*, const unsigned char*,
+                           int*, int*, int*, int*, int*, int, int, int, float,
+                           float, int, hipStream_t);
+int cluster_tile();
 void launch_morton_keys(const float*, const float*, const float*, long*,
                         int, long, hipStream_t);
 void launch_gather_edge_fwd(const void*, const int*, const float*, void*,
@@ -1430,9 +1439,97 @@ std::vector<torch::Tensor> rigid_fit(torch::Tensor src, torch::Tensor dst,
   return {R, t, res, ok};
 }
 
+// rigid_fit once per segment: labels (B,N) i32 in [-1, M) (anything else
+// counts as -1) -> {R (B,M,3,3), t (B,M,3), residual (B,N), ok (B,M) bool};
+// one launch, grid (M, B), no host synchronisation
+std::vector<torch::Tensor> segmented_rigid_fit(
+    torch::Tensor src, torch::Tensor dst, torch::Tensor labels, int64_t M,
+    c10::optional<torch::Tensor> weights, double thresh, int64_t iters) {
+  check_f32(src, "src");
+  check_f32(dst, "dst");
+  TORCH_CHECK(src.dim() == 3 && src.size(2) == 3, "src must be (B,N,3)");
+  TORCH_CHECK(dst.sizes() == src.sizes() && dst.device() == src.device(),
+              "dst must match src in shape and device");
+  const int64_t B = src.size(0), N = src.size(1);
+  TORCH_CHECK(B >= 1 && B <= 65535 && N >= 1, "segmented_rigid_fit requires 1 <= B <= 65535, N >= 1");
+  TORCH_CHECK(N < (1L << 30), "segmented_rigid_fit sizes exceed 32-bit point indexing");
+  TORCH_CHECK(M >= 1 && M <= 65535, "segmented_rigid_fit requires 1 <= num_segments <= 65535");
+  TORCH_CHECK(iters >= 0 && iters <= 64, "segmented_rigid_fit requires 0 <= iters <= 64");
+  TORCH_CHECK(thresh > 0.0, "segmented_rigid_fit requires thresh > 0");
+  TORCH_CHECK(labels.is_cuda() && labels.is_contiguous() &&
+                  labels.scalar_type() == torch::kInt32 && labels.dim() == 2 &&
+                  labels.size(0) == B && labels.size(1) == N &&
+                  labels.device() == src.device(),
+              "labels must be contiguous int32 (B,N) on the device of src");
+  const float* wp = nullptr;
+  if (weights.has_value()) {
+    const torch::Tensor& w = *weights;
+    check_f32(w, "weights");
+    TORCH_CHECK(w.dim() == 2 && w.size(0) == B && w.size(1) == N &&
+                    w.device() == src.device(),
+                "weights must be (B,N) on the device of src");
+    wp = w.data_ptr<float>();
+  }
+  auto R = torch::empty({B, M, 3, 3}, src.options());
+  auto t = torch::empty({B, M, 3}, src.options());
+  auto res = torch::empty({B, N}, src.options());
+  auto ok = torch::empty({B, M}, src.options().dtype(torch::kBool));
+  launch_segmented_rigid_fit(
+      src.data_ptr<float>(), dst.data_ptr<float>(), wp, labels.data_ptr<int>(),
+      R.data_ptr<float>(), t.data_ptr<float>(), res.data_ptr<float>(),
+      reinterpret_cast<unsigned char*>(ok.data_ptr<bool>()), (int)B, (int)N,
+      (int)M, (float)thresh, (int)iters, stream());
+  return {R, t, res, ok};
+}
+
+// xyz, flow (B,N,3) f32, mask (B,N) bool -> {labels (B,N) i32, count (B,M)
+// i32, num_objects (B) i32}: connected components of the radius graph in
+// space and flow, ranked by size; five launches, no host synchronisation.
+// The workspace is allocated here and initialised by the first kernel.
+std::vector<torch::Tensor> cluster_points(torch::Tensor xyz, torch::Tensor flow,
+                                          torch::Tensor mask, double eps,
+                                          double flow_eps, int64_t min_points,
+                                          int64_t M) {
+  check_f32(xyz, "xyz");
+  check_f32(flow, "flow");
+  TORCH_CHECK(xyz.dim() == 3 && xyz.size(2) == 3, "xyz must be (B,N,3)");
+  TORCH_CHECK(flow.sizes() == xyz.sizes() && flow.device() == xyz.device(),
+              "flow must match xyz in shape and device");
+  const int64_t B = xyz.size(0), N = xyz.size(1);
+  TORCH_CHECK(B >= 1 && B <= 65535 && N >= 1, "cluster_points requires 1 <= B <= 65535, N >= 1");
+  // the link grid has nblk (nblk + 1) / 2 workgroups in grid.x
+  TORCH_CHECK(N <= (1L << 22), "cluster_points supports at most 2^22 points per cloud");
+  TORCH_CHECK(M >= 1 && M <= 256, "cluster_points requires 1 <= max_objects <= 256");
+  TORCH_CHECK(min_points >= 3, "cluster_points requires min_points >= 3");
+  TORCH_CHECK(eps >= 0.0 && flow_eps >= 0.0, "cluster_points requires eps, flow_eps >= 0");
+  TORCH_CHECK(mask.is_cuda() && mask.is_contiguous() &&
+                  mask.scalar_type() == torch::kBool && mask.dim() == 2 &&
+                  mask.size(0) == B && mask.size(1) == N &&
+                  mask.device() == xyz.device(),
+              "mask must be contiguous bool (B,N) on the device of xyz");
+  auto iopt = xyz.options().dtype(torch::kInt32);
+  auto ws = torch::empty({5, B, N}, iopt);
+  auto status = torch::empty({B}, iopt);
+  auto labels = torch::empty({B, N}, iopt);
+  auto count = torch::empty({B, M}, iopt);
+  auto nobj = torch::empty({B}, iopt);
+  launch_cluster_points(
+      xyz.data_ptr<float>(), flow.data_ptr<float>(),
+      reinterpret_cast<const unsigned char*>(mask.data_ptr<bool>()),
+      ws.data_ptr<int>(), status.data_ptr<int>(), labels.data_ptr<int>(),
+      count.data_ptr<int>(), nobj.data_ptr<int>(), (int)B, (int)N, (int)M,
+      (float)eps, (float)flow_eps, (int)std::min<int64_t>(min_points, INT32_MAX),
+      stream());
+  return {labels, count, nobj};
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rigid_fit", &rigid_fit);
   m.attr("RIGID_FIT_REG_POINTS") = rigid_fit_reg_points();
+  m.def("segmented_rigid_fit", &segmented_rigid_fit);
+  m.attr("SEGMENTED_FIT_CAPACITY") = segmented_fit_capacity();
+  m.def("cluster_points", &cluster_points);
+  m.attr("CLUSTER_TILE") = cluster_tile();
   m.def("chamfer_fwd", &chamfer_fwd);
   m.def("chamfer_nn_fwd", &chamfer_nn_fwd);
   m.def("chamfer_bwd", &chamfer_bwd);

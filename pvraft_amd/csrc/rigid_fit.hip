@@ -1,5 +1,6 @@
 // K20: robust rigid fit of a flow field (absent in the reference): weighted
-// Kabsch inside a Cauchy IRLS loop, the whole loop in ONE launch.
+// Kabsch inside a Cauchy IRLS loop, the whole loop in ONE launch.  (K22, the
+// same fit once per labelled segment, follows at the end of the file.)
 //
 //   w0_i = prior_i (1 without a prior; 0 for a non-finite coordinate, a
 //          non-finite weight or a weight <= 0)
@@ -547,4 +548,366 @@ void launch_rigid_fit(const float *src, const float *dst, const float *prior,
   else if (N <= RF_REG_POINTS) RF_LAUNCH(4);
   else RF_LAUNCH(0);
 #undef RF_LAUNCH
+}
+
+// ---------------------------------------------------------------------------
+// K22: segmented robust rigid fit -- the loop above once per labelled segment
+// (object) of a cloud, all segments in ONE launch.
+//
+//   labels (B,N) int32: -1 or a segment 0 .. M-1 (anything else counts as -1)
+//   out: R (B,M,3,3), t (B,M,3), ok (B,M); r (B,N) with respect to the point's
+//        own segment, +INF for label -1 or a non-finite coordinate
+//
+// Geometry: grid (M, B), one workgroup of 256 lanes (4 waves) per segment.
+// Objects have 50 to 1000 points: 256 lanes give such a segment one to four
+// points per lane and round, the block fold crosses four waves instead of
+// sixteen, and M * B = 32 .. 64 workgroups spread over as many CUs -- 1024
+// lanes would idle three quarters of them on a typical object and buy
+// nothing, the segments already run in parallel.
+//
+// The workgroup scans its batch element's labels ONCE and compacts its members
+// in ascending index order (wave ballot + prefix over the four waves), so the
+// fold order is fixed and the result bit-reproducible.  Up to SF_CAP = 1024
+// members are kept in LDS (pivot-centred p, d, w0 and the point index, 32 KB),
+// and every round costs in proportion to the segment, not to N.  A larger
+// segment streams instead: every pass walks the labels again and re-reads its
+// members from global memory (L2), like PPL = 0 above.  Workgroup m = 0 also
+// writes the +INF residual of the points that belong to no segment, so every
+// residual is written exactly once and nothing is pre-filled.
+//
+// The math is the one above, unchanged: rf_load, the pivot-centred fp64 sums in
+// two passes of eight, rf_rotation<float> on lane 0, the small-rotation
+// residual; no atomics, no host sync.  The accumulation and the lane-0 solve
+// are written out a second time here on purpose: moving them into inline
+// helpers shared with rigid_fit_kernel was tried and changed that kernel's
+// register allocation and instruction stream (88 -> 78 VGPRs at PPL = 1), and
+// K20 is to stay the code it was.  A change to one copy belongs in the other.
+//
+// Resources (same tool): 118 VGPRs, no AGPRs, scratch 0 bytes, LDS 33264 bytes.
+#define SF_THREADS 256
+#define SF_WAVES (SF_THREADS / WAVE)
+#define SF_CAP 1024
+
+int segmented_fit_capacity() { return SF_CAP; }
+
+struct SfShared {
+  double part[SF_WAVES][RF_HALF];
+  double tot[RF_NSUM];
+  double tfall[3];
+  float E[9];
+  float tp[3];
+  float c[3];
+  int n_use;
+  int ok;
+  int wcnt[SF_WAVES];
+};
+
+// rf_block_sum for four waves
+DEV_INLINE void sf_block_sum(double (&acc)[RF_HALF], SfShared &sh, int base) {
+#pragma unroll
+  for (int j = 0; j < RF_HALF; ++j) acc[j] = rf_wave_sum(acc[j]);
+  if (lane_id() == 0) {
+#pragma unroll
+    for (int j = 0; j < RF_HALF; ++j) sh.part[wave_id()][j] = acc[j];
+  }
+  __syncthreads();
+  if (threadIdx.x < RF_HALF) {
+    double s = 0.0;
+#pragma unroll
+    for (int w = 0; w < SF_WAVES; ++w) s += sh.part[w][threadIdx.x];
+    sh.tot[base + threadIdx.x] = s;
+  }
+  __syncthreads();
+}
+
+__global__ __launch_bounds__(SF_THREADS) void segmented_rigid_fit_kernel(
+    const float *__restrict__ src,    // (B, N, 3)
+    const float *__restrict__ dst,    // (B, N, 3)
+    const float *__restrict__ prior,  // (B, N) or null
+    const int *__restrict__ labels,   // (B, N)
+    float *__restrict__ R_out,        // (B, M, 3, 3)
+    float *__restrict__ t_out,        // (B, M, 3)
+    float *__restrict__ res_out,      // (B, N)
+    unsigned char *__restrict__ ok_out,  // (B, M)
+    int N, int M, float inv_th2, int iters) {
+  __shared__ SfShared sh;
+  __shared__ float mpx[SF_CAP], mpy[SF_CAP], mpz[SF_CAP];
+  __shared__ float mdx[SF_CAP], mdy[SF_CAP], mdz[SF_CAP], mw0[SF_CAP];
+  __shared__ int midx[SF_CAP];
+  const int m = blockIdx.x;
+  const int b = blockIdx.y;
+  const int tid = threadIdx.x;
+  const int seg = b * M + m;
+  src += (long)b * N * 3;
+  dst += (long)b * N * 3;
+  if (prior) prior += (long)b * N;
+  labels += (long)b * N;
+  res_out += (long)b * N;
+
+  // ---- one scan of the labels: ordered compaction of the members ----------
+  int n_mem = 0;  // block-uniform
+  for (int base = 0; base < N; base += SF_THREADS) {
+    const int i = base + tid;
+    const int lab = i < N ? labels[i] : m + 1;
+    const bool mem = i < N && lab == m;
+    if (m == 0 && i < N && (lab < 0 || lab >= M)) res_out[i] = INFINITY;
+    const unsigned long long bal = __ballot(mem);
+    if (lane_id() == 0) sh.wcnt[wave_id()] = __popcll(bal);
+    __syncthreads();
+    int off = n_mem, tot = 0;
+#pragma unroll
+    for (int w = 0; w < SF_WAVES; ++w) {
+      const int c = sh.wcnt[w];
+      off += w < wave_id() ? c : 0;
+      tot += c;
+    }
+    const int pos = off + __popcll(bal & ((1ull << lane_id()) - 1ull));
+    if (mem && pos < SF_CAP) {
+      const RfPoint Q = rf_load(src, dst, prior, i);
+      mpx[pos] = Q.px, mpy[pos] = Q.py, mpz[pos] = Q.pz;
+      mdx[pos] = Q.dx, mdy[pos] = Q.dy, mdz[pos] = Q.dz;
+      mw0[pos] = Q.w0;
+      midx[pos] = i;
+    }
+    n_mem += tot;
+    __syncthreads();
+  }
+  const bool resident = n_mem <= SF_CAP;  // block-uniform
+
+  auto member = [&](int j) __attribute__((always_inline)) {
+    RfPoint Q;
+    Q.px = mpx[j], Q.py = mpy[j], Q.pz = mpz[j];
+    Q.dx = mdx[j], Q.dy = mdy[j], Q.dz = mdz[j];
+    Q.w0 = mw0[j];
+    return Q;
+  };
+
+  double acc[RF_HALF];
+
+  // ---- pass 0: pivot = unweighted mean of the usable src points ----------
+#pragma unroll
+  for (int j = 0; j < RF_HALF; ++j) acc[j] = 0.0;
+  {
+    auto visit = [&](const RfPoint &Q) __attribute__((always_inline)) {
+      const bool use = Q.w0 > 0.f;
+      acc[0] += use ? 1.0 : 0.0;
+      acc[1] += use ? (double)Q.px : 0.0;
+      acc[2] += use ? (double)Q.py : 0.0;
+      acc[3] += use ? (double)Q.pz : 0.0;
+    };
+    if (resident) {
+      for (int j = tid; j < n_mem; j += SF_THREADS) visit(member(j));
+    } else {
+      for (int i = tid; i < N; i += SF_THREADS)
+        if (labels[i] == m) visit(rf_load(src, dst, prior, i));
+    }
+  }
+  sf_block_sum(acc, sh, 0);
+  if (tid == 0) {
+    const double n = sh.tot[0];
+    float c[3] = {0.f, 0.f, 0.f};
+    if (n > 0.0) {
+#pragma unroll
+      for (int a = 0; a < 3; ++a) {
+        const float v = (float)(sh.tot[1 + a] / n);
+        c[a] = isfinite(v) ? v : 0.f;
+      }
+    }
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      sh.c[a] = c[a];
+      sh.tp[a] = 0.f;
+      sh.tfall[a] = 0.0;
+    }
+#pragma unroll
+    for (int a = 0; a < 9; ++a) sh.E[a] = 0.f;
+    sh.n_use = (int)n;
+    sh.ok = 1;
+  }
+  __syncthreads();
+  const float cx = rf_uniform(sh.c[0]), cy = rf_uniform(sh.c[1]),
+              cz = rf_uniform(sh.c[2]);
+  if (resident) {
+    for (int j = tid; j < n_mem; j += SF_THREADS) {
+      if (mw0[j] >= 0.f) {  // unusable members keep p = 0
+        mpx[j] -= cx;
+        mpy[j] -= cy;
+        mpz[j] -= cz;
+      }
+    }
+  }
+  // each lane re-reads only the slots it wrote: no barrier needed here
+
+  // ---- IRLS rounds -------------------------------------------------------
+  float E[9], tp[3];
+#pragma unroll
+  for (int a = 0; a < 9; ++a) E[a] = 0.f;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) tp[a] = 0.f;
+
+  auto resid2 = [&](const RfPoint &Q) __attribute__((always_inline)) {
+    const float ex = fmaf(E[0], Q.px, fmaf(E[1], Q.py, fmaf(E[2], Q.pz, tp[0] - Q.dx)));
+    const float ey = fmaf(E[3], Q.px, fmaf(E[4], Q.py, fmaf(E[5], Q.pz, tp[1] - Q.dy)));
+    const float ez = fmaf(E[6], Q.px, fmaf(E[7], Q.py, fmaf(E[8], Q.pz, tp[2] - Q.dz)));
+    return fmaf(ex, ex, fmaf(ey, ey, ez * ez));
+  };
+  auto centred = [&](RfPoint Q) __attribute__((always_inline)) {
+    if (Q.w0 >= 0.f) {
+      Q.px -= cx;
+      Q.py -= cy;
+      Q.pz -= cz;
+    }
+    return Q;
+  };
+
+  bool ok = true;
+  for (int k = 0; k <= iters; ++k) {
+    for (int half = 0; half < 2; ++half) {
+#pragma unroll
+      for (int j = 0; j < RF_HALF; ++j) acc[j] = 0.0;
+      auto visit = [&](const RfPoint &Q) __attribute__((always_inline)) {
+        float w = fmaxf(Q.w0, 0.f);
+        if (k > 0) {
+          w = w / fmaf(resid2(Q), inv_th2, 1.f);
+          if (!(w > 0.f)) w = 0.f;  // overflowed residual: the point drops out
+        }
+        const double wd = w;
+        const double px = Q.px, py = Q.py, pz = Q.pz;
+        const double dx = Q.dx, dy = Q.dy, dz = Q.dz;
+        if (half == 0) {
+          const double wx = wd * px;
+          acc[0] += wd;
+          acc[1] += wx;
+          acc[2] = fma(wd, py, acc[2]);
+          acc[3] = fma(wd, pz, acc[3]);
+          acc[4] = fma(wd, dx, acc[4]);
+          acc[5] = fma(wd, dy, acc[5]);
+          acc[6] = fma(wd, dz, acc[6]);
+          acc[7] = fma(wx, px + dx, acc[7]);
+        } else {
+          const double wx = wd * px, wy = wd * py, wz = wd * pz;
+          const double qx = px + dx, qy = py + dy, qz = pz + dz;
+          acc[0] = fma(wx, qy, acc[0]);
+          acc[1] = fma(wx, qz, acc[1]);
+          acc[2] = fma(wy, qx, acc[2]);
+          acc[3] = fma(wy, qy, acc[3]);
+          acc[4] = fma(wy, qz, acc[4]);
+          acc[5] = fma(wz, qx, acc[5]);
+          acc[6] = fma(wz, qy, acc[6]);
+          acc[7] = fma(wz, qz, acc[7]);
+        }
+      };
+      if (resident) {
+        for (int j = tid; j < n_mem; j += SF_THREADS) visit(member(j));
+      } else {
+        for (int i = tid; i < N; i += SF_THREADS)
+          if (labels[i] == m) visit(centred(rf_load(src, dst, prior, i)));
+      }
+      sf_block_sum(acc, sh, half * RF_HALF);
+    }
+
+    if (tid == 0) {
+      bool fin = true;
+#pragma unroll
+      for (int j = 0; j < RF_NSUM; ++j) fin = fin && isfinite(sh.tot[j]);
+      const double sw = sh.tot[0];
+      bool good = fin && sw > 0.0 && sh.n_use >= 3;
+      double Ed[3][3], tpd[3];
+      if (fin && sw > 0.0) {
+        const double iw = 1.0 / sw;
+        const double pm[3] = {sh.tot[1] * iw, sh.tot[2] * iw, sh.tot[3] * iw};
+        const double dm[3] = {sh.tot[4] * iw, sh.tot[5] * iw, sh.tot[6] * iw};
+        if (k == 0) {
+#pragma unroll
+          for (int a = 0; a < 3; ++a) sh.tfall[a] = dm[a];
+        }
+        if (good) {
+          double H[3][3];
+#pragma unroll
+          for (int a = 0; a < 3; ++a)
+#pragma unroll
+            for (int c2 = 0; c2 < 3; ++c2)
+              H[a][c2] = sh.tot[7 + 3 * a + c2] - sw * pm[a] * (pm[c2] + dm[c2]);
+          float Hs[3][3], Es[3][3];
+#pragma unroll
+          for (int a = 0; a < 3; ++a)
+#pragma unroll
+            for (int c2 = 0; c2 < 3; ++c2) Hs[a][c2] = (float)H[a][c2];
+          rf_rotation<float>(Hs, Es);
+#pragma unroll
+          for (int a = 0; a < 3; ++a)
+#pragma unroll
+            for (int c2 = 0; c2 < 3; ++c2) Ed[a][c2] = (double)Es[a][c2];
+#pragma unroll
+          for (int a = 0; a < 3; ++a)
+            tpd[a] = dm[a] - (Ed[a][0] * pm[0] + Ed[a][1] * pm[1] +
+                              Ed[a][2] * pm[2]);
+#pragma unroll
+          for (int a = 0; a < 3; ++a)
+            good = good && isfinite(tpd[a]) && isfinite(Ed[a][0]) &&
+                   isfinite(Ed[a][1]) && isfinite(Ed[a][2]);
+        }
+      }
+      if (!good) {
+        // R = I, t = mean of d under the prior weights (0 if none)
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+          tpd[a] = sh.tfall[a];
+#pragma unroll
+          for (int c2 = 0; c2 < 3; ++c2) Ed[a][c2] = 0.0;
+        }
+        sh.ok = 0;
+      }
+#pragma unroll
+      for (int a = 0; a < 3; ++a) {
+        sh.tp[a] = (float)tpd[a];
+#pragma unroll
+        for (int c2 = 0; c2 < 3; ++c2) sh.E[3 * a + c2] = (float)Ed[a][c2];
+      }
+      if (k == iters || !good) {
+        const double cd[3] = {(double)cx, (double)cy, (double)cz};
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+          t_out[seg * 3 + a] = (float)(tpd[a] - (Ed[a][0] * cd[0] + Ed[a][1] * cd[1] +
+                                                 Ed[a][2] * cd[2]));
+#pragma unroll
+          for (int c2 = 0; c2 < 3; ++c2)
+            R_out[seg * 9 + 3 * a + c2] = (float)(Ed[a][c2] + (a == c2 ? 1.0 : 0.0));
+        }
+        ok_out[seg] = good ? 1 : 0;
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int a = 0; a < 9; ++a) E[a] = rf_uniform(sh.E[a]);
+#pragma unroll
+    for (int a = 0; a < 3; ++a) tp[a] = rf_uniform(sh.tp[a]);
+    ok = sh.ok != 0;
+    if (!ok) break;  // block-uniform
+  }
+
+  // ---- residuals of the last fit, members only ---------------------------
+  if (resident) {
+    for (int j = tid; j < n_mem; j += SF_THREADS) {
+      const RfPoint Q = member(j);
+      res_out[midx[j]] = Q.w0 < 0.f ? INFINITY : sqrtf(resid2(Q));
+    }
+  } else {
+    for (int i = tid; i < N; i += SF_THREADS) {
+      if (labels[i] != m) continue;
+      const RfPoint Q = centred(rf_load(src, dst, prior, i));
+      res_out[i] = Q.w0 < 0.f ? INFINITY : sqrtf(resid2(Q));
+    }
+  }
+}
+
+void launch_segmented_rigid_fit(const float *src, const float *dst,
+                                const float *prior, const int *labels, float *R,
+                                float *t, float *res, unsigned char *ok, int B,
+                                int N, int M, float thresh, int iters,
+                                hipStream_t stream) {
+  const float inv_th2 = 1.f / (thresh * thresh);
+  hipLaunchKernelGGL(segmented_rigid_fit_kernel, dim3(M, B), dim3(SF_THREADS), 0,
+                     stream, src, dst, prior, labels, R, t, res, ok, N, M, inv_th2,
+                     iters);
 }

@@ -13,6 +13,9 @@ launch-collapse as the training step, applied to serving.
 
     # flow plus the ego-motion it implies and a static/dynamic split:
     flow, ego = pred.predict_ego_motion(xyz1, xyz2)       # ego.R, ego.t, ...
+
+    # flow plus the moving objects in it, each with its own rigid motion:
+    flow, om = pred.predict_object_motion(xyz1, xyz2)     # om.labels, om.R, ...
 """
 
 from __future__ import annotations
@@ -98,6 +101,20 @@ class Predictor:
         flow = self(xyz1, xyz2)
         ego = ops.ego_motion(xyz1.to(self.device).float(), flow, thresh=thresh, iters=iters)
         return flow, ego
+
+    @torch.no_grad()
+    def predict_object_motion(self, xyz1: torch.Tensor, xyz2: torch.Tensor, **kw):
+        """(flow (B,N,3), ``ops.ObjectMotion``): the usual forward (graph
+        replay as in ``__call__``), then ``ops.object_motion`` of the final
+        flow (ego fit, clustering of the non-static points, one rigid fit
+        per object), run eagerly after the replay without draining the
+        stream.  Keyword arguments go to ``ops.object_motion``.  Works for
+        any predictor batch."""
+        from pvraft_amd import ops
+
+        flow = self(xyz1, xyz2)
+        om = ops.object_motion(xyz1.to(self.device).float(), flow, **kw)
+        return flow, om
 
     @torch.no_grad()
     def predict_dense(self, pc1_full: torch.Tensor, pc2_full: torch.Tensor, k: int = 3,

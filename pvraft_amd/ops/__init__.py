@@ -1079,3 +1079,167 @@ def ego_motion(
     p = pc1.to(R.dtype)
     rigid_flow = p @ R.transpose(1, 2) + t.unsqueeze(1) - p
     return EgoMotion(R, t, residual, static, rigid_flow, ok)
+
+
+# ---------------------------------------------------------------------------
+# moving objects (csrc/cluster.hip, segmented fit in csrc/rigid_fit.hip)
+# ---------------------------------------------------------------------------
+
+
+class ObjectMotion(NamedTuple):
+    """Result of ``object_motion``: labels (B,N) int32, num_objects (B,)
+    int32, count (B,M) int32 from ``cluster_points``; R (B,M,3,3), t (B,M,3),
+    ok (B,M) bool per object; residual (B,N) with respect to the point's own
+    object (+INF outside objects); rigid_flow (B,N,3) piecewise-rigid flow;
+    ego, the ``EgoMotion`` used."""
+
+    labels: Tensor
+    num_objects: Tensor
+    count: Tensor
+    R: Tensor
+    t: Tensor
+    ok: Tensor
+    residual: Tensor
+    rigid_flow: Tensor
+    ego: EgoMotion
+
+
+def cluster_points(
+    xyz: Tensor, flow: Tensor, mask: Tensor, eps: float = 0.5, flow_eps: float = 0.1,
+    min_points: int = 8, max_objects: int = 32,
+) -> Tuple[Tensor, Tensor, Tensor]:
+    """Euclidean + flow-consistency clustering: xyz (B,N,3), flow (B,N,3),
+    mask (B,N) bool -> labels (B,N) int32, count (B,max_objects) int32,
+    num_objects (B,) int32; eps >= 0, flow_eps >= 0 (``float('inf')``
+    disables the flow test), min_points >= 3, 1 <= max_objects <= 256.
+
+    A point is eligible if it is masked and its six numbers are finite.  Two
+    eligible points are linked iff |xyz_i - xyz_j|^2 <= eps^2 and |flow_i -
+    flow_j|^2 <= flow_eps^2 (fp32 sums of squared differences against the
+    fp32 products; a pair within a few ulp of a threshold may fall either
+    way).  The objects are the connected components of this exact radius
+    graph with at least ``min_points`` members, ordered by (size descending,
+    smallest member index ascending); only the first ``max_objects`` are
+    kept.  ``labels`` is the rank of the point's object or -1 (unmasked,
+    non-finite, small component, beyond ``max_objects``), ``count`` the
+    object sizes (0 for unused slots).  The result is canonical: the same
+    integers on every backend and in every run.
+
+    GPU: lock-free union-find over all linked pairs (csrc/cluster.hip), five
+    launches, no host synchronisation, no (N,N) tensor.  Every retry loop in
+    the kernels is capped; should a cap ever be hit, that batch element comes
+    back with all labels -1 and ``num_objects`` = -1 instead of a wrong
+    partition.  Not differentiable.  bf16/fp16 or non-contiguous inputs are
+    upcast / made contiguous here.
+    """
+    if xyz.dim() != 3 or xyz.shape[-1] != 3 or flow.shape != xyz.shape:
+        raise ValueError(f"cluster_points needs xyz, flow (B,N,3), got {tuple(xyz.shape)}, {tuple(flow.shape)}")
+    if mask.shape != xyz.shape[:2]:
+        raise ValueError(f"cluster_points needs mask (B,N), got {tuple(mask.shape)}")
+    if not float(eps) >= 0 or not float(flow_eps) >= 0:
+        raise ValueError(f"cluster_points requires eps, flow_eps >= 0, got {eps}, {flow_eps}")
+    if not int(min_points) >= 3:
+        raise ValueError(f"cluster_points requires min_points >= 3, got {min_points}")
+    if not 1 <= int(max_objects) <= 256:
+        raise ValueError(f"cluster_points requires 1 <= max_objects <= 256, got {max_objects}")
+    B, N = xyz.shape[:2]
+    mask = mask.detach().bool()
+    if _use_hip(xyz) and B > 0 and N > 0:
+        return tuple(_EXT.cluster_points(
+            xyz.detach().float().contiguous(), flow.detach().float().contiguous(), mask.contiguous(),
+            float(eps), float(flow_eps), int(min_points), int(max_objects),
+        ))
+    xyz, flow = _fp32_unless_all_fp64(xyz.detach(), flow.detach())
+    return reference.cluster_points(xyz.contiguous(), flow.contiguous(), mask, float(eps), float(flow_eps),
+                                    int(min_points), int(max_objects))
+
+
+def segmented_rigid_fit(
+    src: Tensor, dst: Tensor, labels: Tensor, num_segments: int, weights: Optional[Tensor] = None,
+    thresh: float = 0.05, iters: int = 0,
+) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """One robust rigid fit per labelled segment: src, dst (B,N,3), labels
+    (B,N) integer in [-1, num_segments) (anything else counts as -1),
+    optional prior weights (B,N) -> R (B,M,3,3), t (B,M,3), residual (B,N),
+    ok (B,M) bool with M = num_segments, 1 <= M <= 65535.
+
+    Per segment this is exactly the loop of ``rigid_fit`` over that
+    segment's points.  ``residual[b,i]`` belongs to i's own segment and is
+    +INF for label -1 and for a non-finite coordinate.  An empty or
+    under-determined segment has ok = False, R = I and t as ``rigid_fit``
+    defines it.
+
+    GPU: one launch, one workgroup per segment, which compacts its members in
+    index order once and keeps up to ``_C.SEGMENTED_FIT_CAPACITY`` of them on
+    chip, so a round costs in proportion to the segment, not to N; no
+    atomics, no host synchronisation, bit-reproducible.  Not differentiable.
+    """
+    if not 0 <= int(iters) <= 64:
+        raise ValueError(f"segmented_rigid_fit requires 0 <= iters <= 64, got {iters}")
+    if not float(thresh) > 0:
+        raise ValueError(f"segmented_rigid_fit requires thresh > 0, got {thresh}")
+    if not 1 <= int(num_segments) <= 65535:
+        raise ValueError(f"segmented_rigid_fit requires 1 <= num_segments <= 65535, got {num_segments}")
+    if src.dim() != 3 or src.shape[-1] != 3 or dst.shape != src.shape:
+        raise ValueError(f"segmented_rigid_fit needs src, dst (B,N,3), got {tuple(src.shape)}, {tuple(dst.shape)}")
+    if labels.shape != src.shape[:2] or labels.is_floating_point() or labels.dtype == torch.bool:
+        raise ValueError(f"segmented_rigid_fit needs integer labels (B,N), got {labels.dtype} {tuple(labels.shape)}")
+    if weights is not None and weights.shape != src.shape[:2]:
+        raise ValueError(f"segmented_rigid_fit needs weights (B,N), got {tuple(weights.shape)}")
+    B, N = src.shape[:2]
+    if _use_hip(src) and B > 0 and N > 0:
+        w = None if weights is None else weights.detach().float().contiguous()
+        lab = labels.detach()
+        if lab.dtype != torch.int32:
+            # out-of-range values of a wider type must not wrap into range
+            lab = torch.where((lab >= 0) & (lab < int(num_segments)), lab, torch.full_like(lab, -1)).int()
+        return tuple(_EXT.segmented_rigid_fit(
+            src.detach().float().contiguous(), dst.detach().float().contiguous(), lab.contiguous(),
+            int(num_segments), w, float(thresh), int(iters),
+        ))
+    if weights is None:
+        src, dst = _fp32_unless_all_fp64(src.detach(), dst.detach())
+    else:
+        src, dst, weights = _fp32_unless_all_fp64(src.detach(), dst.detach(), weights.detach())
+    return reference.segmented_rigid_fit(src.contiguous(), dst.contiguous(), labels.detach(), int(num_segments),
+                                         weights, float(thresh), int(iters))
+
+
+def object_motion(
+    pc1: Tensor, flow: Tensor, ego: Optional[EgoMotion] = None, ego_thresh: float = 0.05, ego_iters: int = 10,
+    eps: float = 0.5, flow_eps: float = 0.1, min_points: int = 8, max_objects: int = 32,
+    thresh: float = 0.05, iters: int = 5,
+) -> ObjectMotion:
+    """Moving objects of a flow field: pc1 (B,N,3), flow (B,N,3) ->
+    ``ObjectMotion``.
+
+      ego    = ego or ego_motion(pc1, flow, ego_thresh, ego_iters)
+      labels, count, num_objects = cluster_points(pc1, flow, ~ego.static,
+                                       eps, flow_eps, min_points, max_objects)
+      R, t, residual, ok = segmented_rigid_fit(pc1, pc1 + flow, labels,
+                                       max_objects, thresh=thresh, iters=iters)
+
+    ``rigid_flow`` is, per point, the flow its object's (R, t) induces where
+    the point belongs to an object with ``ok``, ``ego.rigid_flow`` where the
+    point is static, and the raw flow elsewhere.  The whole call only
+    launches kernels: no host synchronisation.  Not differentiable.
+
+    The defaults (link radii, min_points, thresholds) are untuned guesses at
+    metric driving scenes: nobody has tuned them on real data.
+    """
+    pc1 = pc1.detach()
+    flow = flow.detach()
+    if ego is None:
+        ego = ego_motion(pc1, flow, thresh=ego_thresh, iters=ego_iters)
+    labels, count, num_objects = cluster_points(pc1, flow, ~ego.static, eps, flow_eps, min_points, max_objects)
+    R, t, residual, ok = segmented_rigid_fit(pc1, pc1 + flow, labels, int(max_objects), None, thresh, iters)
+    p = pc1.to(R.dtype)
+    B, N = labels.shape
+    slot = labels.clamp_min(0).long()
+    Rp = R.gather(1, slot.view(B, N, 1, 1).expand(B, N, 3, 3))
+    tp = t.gather(1, slot.view(B, N, 1).expand(B, N, 3))
+    obj_flow = (Rp @ p.unsqueeze(-1)).squeeze(-1) + tp - p
+    in_obj = (labels >= 0) & ok.gather(1, slot)
+    rigid_flow = torch.where(ego.static.unsqueeze(-1), ego.rigid_flow, flow.to(R.dtype))
+    rigid_flow = torch.where(in_obj.unsqueeze(-1), obj_flow, rigid_flow)
+    return ObjectMotion(labels, num_objects, count, R, t, ok, residual, rigid_flow, ego)

@@ -404,3 +404,106 @@ def rigid_fit(
         t = tp - (E @ c.unsqueeze(-1)).squeeze(-1)
         r = torch.where(fin, r, torch.full_like(r, float("inf")))
         return R.contiguous(), t, r, ok
+
+
+# ---------------------------------------------------------------------------
+# Moving objects (absent in the reference): clustering and per-object fits
+# ---------------------------------------------------------------------------
+
+
+def cluster_points(
+    xyz: Tensor, flow: Tensor, mask: Tensor, eps: float = 0.5, flow_eps: float = 0.1,
+    min_points: int = 8, max_objects: int = 32,
+) -> Tuple[Tensor, Tensor, Tensor]:
+    """Connected components of the radius graph in space and flow: xyz
+    (B,N,3), flow (B,N,3), mask (B,N) bool -> labels (B,N) int32, count
+    (B,max_objects) int32, num_objects (B,) int32.
+
+    Eligible points are masked and finite; i ~ j iff |xyz_i - xyz_j|^2 <=
+    eps^2 and |flow_i - flow_j|^2 <= flow_eps^2 (sums of squared differences
+    in the dtype of ``xyz``).  Components of at least ``min_points`` members
+    are ranked by (size descending, smallest member ascending); the first
+    ``max_objects`` are the objects, every other point is labelled -1.
+
+    Dense (N,N) adjacency per batch element; labels spread by taking the
+    minimum over the neighbours, then pointer jumping, until nothing moves
+    (that test is a host synchronisation: this is the oracle, not the GPU
+    path).
+    """
+    with torch.no_grad():
+        B, N, _ = xyz.shape
+        dev = xyz.device
+        M = int(max_objects)
+        labels = torch.full((B, N), -1, dtype=torch.int32, device=dev)
+        count = torch.zeros(B, M, dtype=torch.int32, device=dev)
+        nobj = torch.zeros(B, dtype=torch.int32, device=dev)
+        if N == 0:
+            return labels, count, nobj
+        e = torch.tensor(float(eps), dtype=xyz.dtype, device=dev)
+        fe = torch.tensor(float(flow_eps), dtype=xyz.dtype, device=dev)
+        e2, fe2 = e * e, fe * fe
+        ar = torch.arange(N, device=dev)
+        for b in range(B):
+            el = mask[b].bool() & torch.isfinite(xyz[b]).all(-1) & torch.isfinite(flow[b]).all(-1)
+            p = torch.where(el.unsqueeze(-1), xyz[b], torch.zeros_like(xyz[b]))
+            f = torch.where(el.unsqueeze(-1), flow[b], torch.zeros_like(flow[b]))
+            dp = p.unsqueeze(1) - p.unsqueeze(0)
+            d2 = dp[..., 0] * dp[..., 0] + dp[..., 1] * dp[..., 1] + dp[..., 2] * dp[..., 2]
+            df = f.unsqueeze(1) - f.unsqueeze(0)
+            f2 = df[..., 0] * df[..., 0] + df[..., 1] * df[..., 1] + df[..., 2] * df[..., 2]
+            adj = (d2 <= e2) & (f2 <= fe2) & el.unsqueeze(0) & el.unsqueeze(1)
+            adj = adj | torch.eye(N, dtype=torch.bool, device=dev)
+            del dp, df, d2, f2
+            lab = ar.clone()
+            big = torch.full((), N, dtype=lab.dtype, device=dev)
+            while True:
+                new = torch.where(adj, lab.unsqueeze(0), big).min(dim=1)[0]
+                new = new[new]  # pointer jumping: labels are member indices
+                new = new[new]
+                if torch.equal(new, lab):
+                    break
+                lab = new
+            size = torch.zeros(N, dtype=torch.long, device=dev).scatter_add_(0, lab, el.long())
+            qual = (size >= int(min_points)) & (lab == ar) & el
+            # size descending, root ascending
+            key = torch.where(qual, size * (N + 1) + (N - ar), torch.zeros_like(size))
+            order = key.argsort(descending=True, stable=True)
+            rank_of = torch.full((N,), -1, dtype=torch.long, device=dev)
+            rank_of[order] = ar
+            keep = qual & (rank_of < M)
+            rank_of = torch.where(keep, rank_of, torch.full_like(rank_of, -1))
+            labels[b] = torch.where(el, rank_of[lab], torch.full_like(lab, -1)).int()
+            slot = torch.where(keep, rank_of, torch.full_like(rank_of, M))
+            cnt = torch.zeros(M + 1, dtype=torch.long, device=dev).scatter_add_(0, slot, size)
+            count[b] = cnt[:M].int()
+            nobj[b] = keep.sum().int()
+        return labels, count, nobj
+
+
+def segmented_rigid_fit(
+    src: Tensor, dst: Tensor, labels: Tensor, num_segments: int, weights: Optional[Tensor] = None,
+    thresh: float = 0.05, iters: int = 0,
+) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """``rigid_fit`` once per segment, with the membership as weights: src,
+    dst (B,N,3), labels (B,N) in [-1, num_segments) (anything else counts as
+    -1) -> R (B,M,3,3), t (B,M,3), residual (B,N) with respect to the
+    point's own segment (+INF outside every segment), ok (B,M)."""
+    with torch.no_grad():
+        B, N, _ = src.shape
+        M = int(num_segments)
+        dt, dev = src.dtype, src.device
+        Rs, ts, oks = [], [], []
+        residual = torch.full((B, N), float("inf"), dtype=dt, device=dev)
+        prior = torch.ones(B, N, dtype=dt, device=dev) if weights is None else weights.to(dt)
+        for m in range(M):
+            member = labels == m
+            w = torch.where(member, prior, torch.zeros_like(prior))
+            R, t, r, ok = rigid_fit(src, dst, w, thresh, iters)
+            residual = torch.where(member, r, residual)
+            Rs.append(R)
+            ts.append(t)
+            oks.append(ok)
+        if M == 0:
+            return (torch.zeros(B, 0, 3, 3, dtype=dt, device=dev), torch.zeros(B, 0, 3, dtype=dt, device=dev),
+                    residual, torch.zeros(B, 0, dtype=torch.bool, device=dev))
+        return torch.stack(Rs, 1), torch.stack(ts, 1), residual, torch.stack(oks, 1)

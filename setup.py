@@ -36,6 +36,7 @@ SOURCES = [
     "pvraft_amd/csrc/chamfer.hip",
     "pvraft_amd/csrc/flow_smooth.hip",
     "pvraft_amd/csrc/rigid_fit.hip",
+    "pvraft_amd/csrc/cluster.hip",
 ]
 
 setup(

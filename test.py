@@ -23,6 +23,12 @@ def parse_args():
     parser.add_argument("--ego_motion", help="also fit the ego-motion of the predicted flow and report ego_* / rigid_* metrics", action="store_true")
     parser.add_argument("--ego_thresh", help="static/dynamic residual threshold of the ego-motion fit (m)", default=0.05, type=float)
     parser.add_argument("--ego_iters", help="reweighting rounds of the ego-motion fit", default=10, type=int)
+    parser.add_argument("--object_motion", help="also segment the moving objects of the predicted flow (implies the ego-motion fit) and report obj_* / objrigid_* metrics", action="store_true")
+    parser.add_argument("--obj_eps", help="spatial link radius of the object clustering (m)", default=0.5, type=float)
+    parser.add_argument("--obj_flow_eps", help="flow link radius of the object clustering (m)", default=0.1, type=float)
+    parser.add_argument("--obj_min_points", help="smallest object, in points", default=8, type=int)
+    parser.add_argument("--obj_max_objects", help="objects kept per sample, largest first", default=32, type=int)
+    parser.add_argument("--obj_iters", help="reweighting rounds of the per-object fits", default=5, type=int)
     return parser.parse_args()
 
 
