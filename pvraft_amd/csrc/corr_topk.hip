@@ -22,12 +22,22 @@
 //     Sample and sweep values are BITWISE equal (identical MFMA fragment
 //     and k-block order), so the threshold counts are exact -- and the
 //     kernel CHECKS them: rows whose direct count exceeded K, whose
-//     coverage missed K, or whose band overflowed get their thresholds
-//     adjusted from the EXACT counts and are re-swept (<= 4 rounds; only
-//     workgroups owning failed rows re-sweep).  After the loop only
-//     massive value ties (degenerate inputs) can remain short, and any K
-//     of tied values is a correct top-K SET -- remaining slots pad from
-//     the band head, like the round-1 kernel.
+//     coverage missed K, or whose band overflowed are re-swept (only
+//     workgroups owning failed rows re-sweep).  The sample can be
+//     arbitrarily wrong -- caller-ordered columns whose every ST-th entry
+//     is biased, or K = 1024 where E[band] is already 616 of CT_CAP -- so
+//     the retry does not extrapolate: every swept threshold is classified
+//     by its exact count into "valid P_hi" (count above <= K) or "valid
+//     P_lo" (count at-or-above >= K), each row keeps the tightest pair
+//     [L, H], the first CT_GUESS retries extend a missing end by 4x the
+//     span, and from then on the pair is bisected in fkey space until the
+//     band between fits.  That ends within CT_MAXIT sweeps for ANY finite
+//     input and yields the exact top-K SET (of the kernel's fp32 values)
+//     with K distinct indices, unless two adjacent float values at the
+//     K boundary together hold more than CT_CAP entries; tie groups up to
+//     CT_CAP / 2 are therefore always exact.  Only beyond that do
+//     remaining slots pad from the band head (duplicate indices), like
+//     the round-1 kernel.
 //   kernel C (select): a wave per row extracts the remaining
 //     K - count(>P_hi) largest entries from the band.
 //
@@ -49,6 +59,10 @@ typedef __attribute__((ext_vector_type(4))) float f32x4;
 #define CT_RWA 16      // rows per workgroup, sample kernel
 #define CT_RWB 32      // rows per workgroup, sweep kernel
 #define CT_CPAD 8      // bf16 padding per LDS f1 row
+#define CT_GUESS 3     // retries that may extend the thresholds by a span guess
+#define CT_MAXIT 38    // 1 + CT_GUESS guesses + 32-bit bisection + final, rounded up
+#define CT_KEY_PINF 0xFF800000u  // fkey(+inf): above every finite value
+#define CT_KEY_NINF 0x007FFFFFu  // fkey(-inf): below every finite value
 
 // ------------------------------------------------------------- kernel A
 
@@ -140,6 +154,7 @@ __global__ __launch_bounds__(CT_THREADS) void corr_sweep_kernel(
   __shared__ __hip_bfloat16 s_f1[CT_RWB][C + CT_CPAD];
   __shared__ float s_phi[CT_RWB], s_plo[CT_RWB];
   __shared__ unsigned s_hi[CT_RWB], s_bd[CT_RWB];
+  __shared__ unsigned s_H[CT_RWB], s_L[CT_RWB];  // retry bracket (fkey space)
   __shared__ unsigned s_active;
 
   const int b = blockIdx.z;
@@ -161,6 +176,8 @@ __global__ __launch_bounds__(CT_THREADS) void corr_sweep_kernel(
     s_plo[r] = n < N ? thr[((long)b * N + n) * 2 + 1] : INFINITY;
     s_hi[r] = 0;
     s_bd[r] = 0;
+    s_H[r] = CT_KEY_PINF;
+    s_L[r] = CT_KEY_NINF;
   }
   if (threadIdx.x == 0) s_active = (unsigned)-1;
   __syncthreads();
@@ -168,7 +185,7 @@ __global__ __launch_bounds__(CT_THREADS) void corr_sweep_kernel(
   const int frow = lane & 15;
   const int koff = (lane >> 4) * 8;
   const int nfrag = (M + 15) / 16;
-  for (int iter = 0; iter < 4 && s_active != 0u; ++iter) {
+  for (int iter = 0; iter < CT_MAXIT && s_active != 0u; ++iter) {
     // register copies of this lane's row thresholds/active bits: the LDS
     // counter atomics below alias LDS for the compiler, which would
     // otherwise re-read s_phi/s_plo/s_active per emitted element
@@ -238,32 +255,63 @@ __global__ __launch_bounds__(CT_THREADS) void corr_sweep_kernel(
         atomicAnd(&s_active, ~(1u << r));
         continue;
       }
+      // both counters are exact (they keep counting past K and CT_CAP):
+      // chi = count(v > P_hi), chi + cbd = count(v >= P_lo)
       const unsigned chi = s_hi[r], cbd = s_bd[r];
       const bool over_hi = chi > (unsigned)K;
-      const bool under = chi + min(cbd, (unsigned)CT_CAP) < (unsigned)K;
-      const bool over_bd = cbd > (unsigned)CT_CAP && chi + cbd >= (unsigned)K;
-      if ((!over_hi && !under && !over_bd) || iter == 3) {
-        // done -- or out of retries (massive ties): KEEP the last sweep's
-        // counters/buffers; kernel C pads what is short
+      const bool under = chi + cbd < (unsigned)K;
+      const bool over_bd = !over_hi && !under && cbd > (unsigned)CT_CAP;
+      const unsigned khi = fkey(s_phi[r]), klo = fkey(s_plo[r]);
+      if ((!over_hi && !under && (!over_bd || khi - klo <= 1u)) ||
+          iter == CT_MAXIT - 1) {
+        // done -- or P_lo and P_hi are adjacent floats that together hold
+        // more than CT_CAP entries (massive ties): KEEP the last sweep's
+        // counters/buffers; kernel C pads what is short.  (CT_MAXIT is not
+        // reached before that; the test only keeps the last buffers
+        // should the constants ever disagree.)
         atomicAnd(&s_active, ~(1u << r));
         continue;
       }
+      // every swept threshold is classified by its exact count:
+      //   count(v > t) <= K  -> t can serve as P_hi; H is the lowest such
+      //   count(v >= t) >= K -> t can serve as P_lo; L is the highest such
+      unsigned H = s_H[r], L = s_L[r];
+      if (over_hi) L = max(L, khi); else H = min(H, khi);
+      if (under) H = min(H, klo); else L = max(L, klo);
+      const bool haveH = H != CT_KEY_PINF, haveL = L != CT_KEY_NINF;
       const float span = s_phi[r] - s_plo[r] + 1e-6f * (1.f + fabsf(s_phi[r]));
-      if (over_hi) {
-        // too many strict accepts: push P_hi above them, band takes over
-        s_plo[r] = s_phi[r];
-        s_phi[r] = s_phi[r] + span * 4.f;
-      } else if (under) {
-        // coverage short of K: band region grows downward
-        s_phi[r] = s_plo[r];
-        s_plo[r] = s_plo[r] - span * 4.f;
-      } else {
-        // band overflowed its buffer: shrink the band span by the COUNT
-        // ratio (cbd is the true count), with slack for the next sweep
-        const float f =
-            fminf(1.f, (float)(K - (int)chi + 64) / (float)cbd * 1.25f);
-        s_plo[r] = s_phi[r] - (s_phi[r] - s_plo[r]) * f;
+      // bisect the bracket in key space: P_hi stays at H, P_lo goes to the
+      // middle.  Too few -> the middle becomes H, band too large -> it
+      // becomes L; H - L halves every sweep.
+      float nphi = fkey_inv(H);
+      float nplo = fkey_inv(H > L ? L + (H - L) / 2u : H);
+      if (iter < CT_GUESS) {
+        // the first retries size the next band from the exact counts
+        // (locally linear density), which lands at once on ordinary rows
+        if (!haveH) {
+          // too many strict accepts and no upper end yet: push P_hi above
+          // them, the band takes over from the old P_hi
+          nplo = fkey_inv(L);
+          nphi = nplo + span * 4.f;
+        } else if (!haveL) {
+          // coverage short of K and no lower end yet: the band restarts
+          // at H and grows down by the missing count plus slack
+          const float miss = (float)((unsigned)K - chi - cbd) + 128.f;
+          nplo = nphi - span * fminf(4.f, miss / (float)max(cbd, 1u));
+        } else if (over_bd && khi == H && klo == L &&
+                   (unsigned)K - chi + 96u < (unsigned)CT_CAP) {
+          // band overflowed its buffer: shrink its span by the COUNT
+          // ratio (cbd is the true count) to between the need and CT_CAP
+          const float need = (float)((unsigned)K - chi);
+          const float tgt = fminf(1.25f * (need + 64.f), 0.5f * (need + CT_CAP));
+          const float g = nphi - (nphi - s_plo[r]) * (tgt / (float)cbd);
+          if (fkey(g) > L && fkey(g) < H) nplo = g;
+        }
       }
+      s_H[r] = H;
+      s_L[r] = L;
+      s_phi[r] = nphi;
+      s_plo[r] = nplo;
       s_hi[r] = 0;
       s_bd[r] = 0;
     }

@@ -16,14 +16,26 @@
 //           instead of N.  Everything else is rejected with ZERO atomics.
 //   select: a wave extracts the exact k smallest from the buffer.
 //
-//   Underflow (buffer < k: ~1e-5 per query for k=32 by the Poisson tail)
-//   widens tau 4x and re-sweeps the active queries; after 3 widenings the
-//   remaining slots pad with the query itself (degenerate tie clouds --
-//   same semantics as round 1; downstream consumers are set/order
-//   invariant and edge features of self-pairs are zero).
+//   The sweep counts exactly, so a miss is always seen: underflow (< k
+//   collected; ~1e-5 per query on unordered clouds, but every query when
+//   the strided sample misrepresents the cloud, e.g. caller-ordered points
+//   whose every ST-th point is an outlier) and buffer overflow (> CAP)
+//   re-sweep the workgroup's failed queries with a new tau.  Each query
+//   keeps a bracket [lo, hi] of thresholds known to give too few / too
+//   many; the first KNN_GUESS retries take a count-based guess when it
+//   falls inside the bracket (power-law widening on underflow, the exact
+//   2k-th smallest collected distance on overflow), then the bracket is
+//   bisected in float-bit space, so the loop ends within KNN_MAXIT sweeps
+//   for ANY finite input.  The result is the exact k-nearest set (on the
+//   kernel's fp32 distances) whenever some threshold has k <= count <= CAP,
+//   i.e. unless more than CAP - k points tie at one boundary distance.
+//   Only then is the k-th neighbour taken from an arbitrary CAP of the
+//   tied points, or do remaining slots pad with the query itself (a valid
+//   neighbour: downstream consumers are set/order invariant and edge
+//   features of self-pairs are zero).
 //
 //   For small clouds (ST == 1) the sample IS the cloud, tau is the exact
-//   min(2k, N)-th distance, and no underflow is possible.
+//   min(2k, N)-th distance, and only ties can miss the window.
 //
 // Candidate tiles (TILE_PTS x 3 fp32) are staged in LDS and shared by
 // QB=8 queries per workgroup; grid (ceil(N/QB), B) fills the chip.
@@ -42,6 +54,8 @@
 #define CAP 256         // collect-buffer capacity per query
 #define SAMP 1024       // max sample size per query
 #define KNN_MAXK 48     // model uses 32 (reference extractor.py:10)
+#define KNN_GUESS 3     // retries that may use a count-based guess for tau
+#define KNN_MAXIT 36    // 1 + KNN_GUESS guesses + 31-bit bisection, rounded up
 
 __global__ __launch_bounds__(KNN_THREADS) void knn_select_kernel(
     const float *__restrict__ xyz,  // (B, N, 3)
@@ -52,6 +66,7 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_select_kernel(
   __shared__ int s_bi[QB][CAP];
   __shared__ unsigned s_cnt[QB];  // collect counters
   __shared__ float s_tau[QB];
+  __shared__ int s_lo[QB], s_hi[QB];  // tau bracket (float bits), see pass B
   __shared__ unsigned s_active;   // queries still needing a sweep
   __shared__ float s_q[QB][3];
 
@@ -76,6 +91,8 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_select_kernel(
     s_q[threadIdx.x][1] = cloud[qq * 3 + 1];
     s_q[threadIdx.x][2] = cloud[qq * 3 + 2];
     s_cnt[threadIdx.x] = 0;
+    s_lo[threadIdx.x] = -1;          // below every distance
+    s_hi[threadIdx.x] = 0x7f800000;  // +inf: above every finite distance
   }
   if (threadIdx.x == 0) s_active = (1u << QB) - 1;
   __syncthreads();
@@ -122,9 +139,11 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_select_kernel(
   }
   __syncthreads();
 
-  // ---- pass B: collect d <= tau; retarget tau from the EXACT count on
-  // underflow (< k) or buffer overflow (> CAP) and re-sweep
-  for (int iter = 0; iter < 4 && s_active != 0; ++iter) {
+  // ---- pass B: collect d <= tau; on underflow (< k) or buffer overflow
+  // (> CAP) move tau inside the bracket of exact counts and re-sweep.
+  // d >= 0, so the int bit pattern of a distance is order-preserving and
+  // the bracket lives in bit space: count(d <= lo) < k, count(d <= hi) > CAP.
+  for (int iter = 0; iter < KNN_MAXIT && s_active != 0; ++iter) {
     const unsigned active = s_active;
     float tau[QB];
 #pragma unroll
@@ -157,18 +176,59 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_select_kernel(
       }
     }
     __syncthreads();
-    if (threadIdx.x < QB) {
-      const int qi = threadIdx.x;
-      if (active >> qi & 1u) {
-        const unsigned c = s_cnt[qi];
-        if ((c >= (unsigned)k && c <= (unsigned)CAP) || q0 + qi >= N ||
-            (iter == 3)) {
+    // exact-count check, a wave per query (wave-uniform control flow)
+    for (int qi = wave_id(); qi < QB; qi += KNN_THREADS / WAVE) {
+      if (!(active >> qi & 1u)) continue;
+      const unsigned c = s_cnt[qi];
+      if ((c >= (unsigned)k && c <= (unsigned)CAP) || q0 + qi >= N) {
+        if (lane_id() == 0) atomicAnd(&s_active, ~(1u << qi));
+        continue;
+      }
+      const float t = s_tau[qi];
+      int lo = s_lo[qi], hi = s_hi[qi];
+      int guess;
+      if (c < (unsigned)k) {
+        lo = max(lo, __float_as_int(t));
+        // retarget E[count] to 4k using count ~ tau^1.5 (3-D volume);
+        // +epsilon escapes tau == 0 (coincident points)
+        const float ratio = (4.f * k) / (float)max(c, 2u);
+        guess = __float_as_int(t * __powf(ratio, 0.6667f) + 1e-30f);
+      } else {
+        hi = min(hi, __float_as_int(t));
+        // the 2k-th smallest of the CAP collected distances is a true
+        // upper bound: count(d <= it) >= 2k, so it can never underflow
+        // (radix descent like wave_rank_key, on ascending keys and rolled:
+        // this is the cold path, keep its code small)
+        int kv[CAP / WAVE];
+#pragma unroll
+        for (int s = 0; s < CAP / WAVE; ++s)
+          kv[s] = __float_as_int(s_bd[qi][lane_id() + s * WAVE]);
+        // smallest g with count(kv <= g) >= 2k: clear bits from the top
+        guess = 0x7fffffff;
+#pragma unroll 1
+        for (int bit = 30; bit >= 0; --bit) {
+          const int cand = guess & ~(1 << bit);
+          int cn = 0;
+#pragma unroll
+          for (int s = 0; s < CAP / WAVE; ++s) cn += kv[s] <= cand;
+          if (wave_sum_int(cn) >= 2 * k) guess = cand;
+        }
+      }
+      // the first retries trust the guess while it lies strictly inside
+      // the bracket; after that bisect, which halves hi - lo every sweep
+      if (iter >= KNN_GUESS || guess <= lo || guess >= hi)
+        guess = lo + (hi - lo) / 2;
+      if (lane_id() == 0) {
+        if (guess <= lo || iter == KNN_MAXIT - 1) {
+          // hi == lo + 1: one distance value alone holds more than
+          // CAP - k points.  Keep this sweep's buffer; the tail pads.
+          // (KNN_MAXIT is not reached before that; the test only keeps
+          // the last buffer should the constants ever disagree.)
           atomicAnd(&s_active, ~(1u << qi));
         } else {
-          // retarget E[count] to 4k using count ~ tau^1.5 (3-D volume);
-          // +epsilon escapes tau == 0 (coincident points)
-          const float ratio = (4.f * k) / (float)max(c, 2u);
-          s_tau[qi] = s_tau[qi] * __powf(ratio, 0.6667f) + 1e-30f;
+          s_lo[qi] = lo;
+          s_hi[qi] = hi;
+          s_tau[qi] = __int_as_float(guess);
           s_cnt[qi] = 0;
         }
       }

@@ -3,9 +3,12 @@
 //
 // Same histogram-select idea as the kNN graph kernel, keyed on the
 // order-preserving unsigned map of floats, MSB-first 8-bit rounds:
-// correlation values cluster within one exponent, so up to three refine
-// rounds (exponent byte, then two mantissa bytes) narrow the threshold
-// until the boundary bin fits the wave-select buffer.  One workgroup per
+// correlation values cluster within one exponent, so refine rounds
+// (exponent byte, then the mantissa bytes) narrow the threshold until the
+// boundary bin fits the wave-select buffer.  A bin that still does not fit
+// after all four bytes holds a single value, and any `need` of its entries
+// complete the set, so the result is the exact top-K SET with K distinct
+// indices for every finite input, ties of any size included.  One workgroup per
 // row; the row is staged once into LDS (M <= 8192 -> 32 KB) and every
 // pass reads it from there.
 //
@@ -35,7 +38,7 @@ __global__ __launch_bounds__(TK_THREADS) void topk_rows_kernel(
   __shared__ int s_bi[TK_CAP];
   __shared__ unsigned s_acc, s_bcnt, s_state[3];
   // s_state: [0] = threshold prefix (bytes chosen so far, left-aligned)
-  //          [1] = number of refined bytes (1..3)
+  //          [1] = number of refined bytes (1..4)
   //          [2] = remaining slots to take at the exact threshold byte
 
   const int row = blockIdx.x;
@@ -52,7 +55,7 @@ __global__ __launch_bounds__(TK_THREADS) void topk_rows_kernel(
   int need = K;
   int nbytes = 0;
   const int wv = wave_id();
-  for (int round = 0; round < 3; ++round) {
+  for (int round = 0; round < 4; ++round) {
     __syncthreads();
     for (int i = threadIdx.x; i < 256 * (TK_THREADS / WAVE); i += TK_THREADS)
       ((unsigned *)s_hist)[i] = 0;
@@ -88,8 +91,9 @@ __global__ __launch_bounds__(TK_THREADS) void topk_rows_kernel(
       s_state[0] = prefix | ((unsigned)T << shift);
       s_state[1] = (unsigned)(round + 1);
       s_state[2] = (unsigned)(need - (int)cum);
-      // stop refining once the threshold bin fits the boundary buffer
-      if (s_hist[0][T] <= TK_CAP - 8 || round == 2) s_state[1] |= 0x100u;
+      // stop refining once the threshold bin fits the boundary buffer;
+      // after the fourth byte the bin is one value and needs no buffer
+      if (s_hist[0][T] <= TK_CAP - 8 || round == 3) s_state[1] |= 0x100u;
     }
     __syncthreads();
     prefix = s_state[0];
@@ -100,7 +104,11 @@ __global__ __launch_bounds__(TK_THREADS) void topk_rows_kernel(
 
   // collect: accepted = key prefix strictly greater than the threshold
   // prefix at the examined depth; boundary = exactly equal.
+  // At full depth (nbytes == 4) the boundary entries are one tied value
+  // and exactly K - need keys lie above it: the first `need` arrivals go
+  // straight to the tail slots, whatever the size of the tie group.
   const int shift = 32 - 8 * nbytes;
+  const bool tied = nbytes == 4;
   __syncthreads();
   for (int i = threadIdx.x; i < M; i += TK_THREADS) {
     const float v = s_row[i];
@@ -112,13 +120,19 @@ __global__ __launch_bounds__(TK_THREADS) void topk_rows_kernel(
       out_i[(long)row * K + slot] = i;
     } else if (kp == tp) {
       const unsigned p = atomicAdd(&s_bcnt, 1u);
-      if (p < TK_CAP) {
+      if (tied) {
+        if (p < (unsigned)need) {
+          out_v[(long)row * K + K - 1 - p] = v;
+          out_i[(long)row * K + K - 1 - p] = i;
+        }
+      } else if (p < TK_CAP) {
         s_bv[p] = v;
         s_bi[p] = i;
       }
     }
   }
   __syncthreads();
+  if (tied) return;  // uniform: nbytes is the same in every thread
 
   // wave 0 selects the remaining `need` LARGEST from the boundary buffer
   // (wave_extract_min keeps every slot access statically indexed -- a
@@ -145,7 +159,8 @@ __global__ __launch_bounds__(TK_THREADS) void topk_rows_kernel(
         out_i[(long)row * K + base + r] = pay;
       }
     }
-    // degenerate ties beyond CAP: pad with the first boundary entry
+    // not reached for finite rows (the boundary bin fits the buffer
+    // here, so take == need); non-finite rows pad with the first entry
     if (lane == 0)
       for (int r = base + take; r < K; ++r) {
         out_v[(long)row * K + r] = L > 0 ? s_bv[0] : -INFINITY;

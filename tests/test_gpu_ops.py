@@ -242,7 +242,8 @@ def test_pw_wgrad_mfma_matches_einsum(B, Co, Ci, S):
 
 def test_knn_graph_degenerate_ties():
     """All-identical points: every distance ties; the kernel must still emit
-    k valid indices per query (histogram refine + boundary overflow path)."""
+    k valid indices per query (collect-buffer overflow with a collapsed
+    threshold bracket: the tie-overflow path)."""
     xyz = torch.zeros(1, 300, 3, device=dev())
     idx = ops.knn_graph(xyz, 16)
     assert idx.shape == (1, 300, 16)
