@@ -32,6 +32,17 @@ void launch_segmented_rigid_fit(const float*, const float*, const float*,
                                 unsigned char*, int, int, int, float, int,
                                 hipStream_t);
 int segmented_fit_capacity();
+void launch_plane_hypotheses(const float*, const unsigned char*, int*, float*,
+                             int*, int, int, int, unsigned, float, float, float,
+                             float, float, hipStream_t);
+void launch_plane_refine(const float*, const unsigned char*, const float*,
+                         const int*, float*, float*, float*, unsigned char*,
+                         unsigned char*, int*, int*, int*, unsigned char*,
+                         double*, int, int, int, int, double, float, float,
+                         float, float, hipStream_t);
+int plane_score_tile();
+int plane_score_block();
+int plane_refine_block();
 void launch_cluster_points(const float*, const float*, const unsigned char*,
                            int*, int*, int*, int*, int*, int, int, int, float,
                            float, int, hipStream_t);
@@ -1523,7 +1534,76 @@ std::vector<torch::Tensor> cluster_points(torch::Tensor xyz, torch::Tensor flow,
   return {labels, count, nobj};
 }
 
+// Ground-plane fit (csrc/plane_fit.hip).  xyz (B,N,3) f32, optional mask (B,N)
+// bool.  up / cos2 / thresh2 arrive already rounded to fp32 by the caller so
+// every backend tests against the same numbers.  refine_iters < 0 stops after
+// the scores: {idx (B,H,3) i32, count (B,H) i32}.  Otherwise {normal (B,3),
+// offset (B), height (B,N), ground (B,N) bool, inlier (B,N) bool, count (B)
+// i32, best (B) i32, rounds (B) i32, ok (B) bool}.  Four launches, no host
+// synchronisation.
+std::vector<torch::Tensor> plane_fit(torch::Tensor xyz,
+                                     c10::optional<torch::Tensor> mask,
+                                     double thresh, double thresh2, double cos2,
+                                     double upx, double upy, double upz,
+                                     int64_t H, int64_t refine_iters,
+                                     int64_t seed) {
+  check_f32(xyz, "xyz");
+  TORCH_CHECK(xyz.dim() == 3 && xyz.size(2) == 3, "xyz must be (B,N,3)");
+  const int64_t B = xyz.size(0), N = xyz.size(1);
+  TORCH_CHECK(B >= 1 && B <= 65535 && N >= 1, "plane_fit requires 1 <= B <= 65535, N >= 1");
+  TORCH_CHECK(N < (1L << 30), "plane_fit sizes exceed 32-bit point indexing");
+  TORCH_CHECK(H >= 1 && H <= 4096, "plane_fit requires 1 <= hypotheses <= 4096");
+  TORCH_CHECK(refine_iters <= 16, "plane_fit requires refine_iters <= 16");
+  TORCH_CHECK(thresh > 0.0 && thresh2 > 0.0, "plane_fit requires thresh > 0");
+  const unsigned char* mp = nullptr;
+  if (mask.has_value()) {
+    const torch::Tensor& m = *mask;
+    TORCH_CHECK(m.is_cuda() && m.is_contiguous() &&
+                    m.scalar_type() == torch::kBool && m.dim() == 2 &&
+                    m.size(0) == B && m.size(1) == N &&
+                    m.device() == xyz.device(),
+                "mask must be contiguous bool (B,N) on the device of xyz");
+    mp = reinterpret_cast<const unsigned char*>(m.data_ptr<bool>());
+  }
+  auto iopt = xyz.options().dtype(torch::kInt32);
+  auto bopt = xyz.options().dtype(torch::kBool);
+  auto idx = torch::empty({B, H, 3}, iopt);
+  auto cnt = torch::empty({B, H}, iopt);
+  auto rec = torch::empty({B, H, 8}, xyz.options());
+  launch_plane_hypotheses(xyz.data_ptr<float>(), mp, idx.data_ptr<int>(),
+                          rec.data_ptr<float>(), cnt.data_ptr<int>(), (int)B,
+                          (int)N, (int)H, (unsigned)(seed & 0xffffffffL),
+                          (float)upx, (float)upy, (float)upz, (float)cos2,
+                          (float)thresh2, stream());
+  if (refine_iters < 0) return {idx, cnt};
+  auto normal = torch::empty({B, 3}, xyz.options());
+  auto offset = torch::empty({B}, xyz.options());
+  auto height = torch::empty({B, N}, xyz.options());
+  auto ground = torch::empty({B, N}, bopt);
+  auto inlier = torch::empty({B, N}, bopt);
+  auto count = torch::empty({B}, iopt);
+  auto best = torch::empty({B}, iopt);
+  auto rounds = torch::empty({B}, iopt);
+  auto ok = torch::empty({B}, bopt);
+  auto plane64 = torch::empty({B, 8}, xyz.options().dtype(torch::kFloat64));
+  launch_plane_refine(
+      xyz.data_ptr<float>(), mp, rec.data_ptr<float>(), cnt.data_ptr<int>(),
+      normal.data_ptr<float>(), offset.data_ptr<float>(),
+      height.data_ptr<float>(),
+      reinterpret_cast<unsigned char*>(ground.data_ptr<bool>()),
+      reinterpret_cast<unsigned char*>(inlier.data_ptr<bool>()),
+      count.data_ptr<int>(), best.data_ptr<int>(), rounds.data_ptr<int>(),
+      reinterpret_cast<unsigned char*>(ok.data_ptr<bool>()),
+      plane64.data_ptr<double>(), (int)B, (int)N, (int)H, (int)refine_iters,
+      thresh, (float)upx, (float)upy, (float)upz, (float)cos2, stream());
+  return {normal, offset, height, ground, inlier, count, best, rounds, ok};
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  m.def("plane_fit", &plane_fit);
+  m.attr("PLANE_SCORE_TILE") = plane_score_tile();
+  m.attr("PLANE_SCORE_BLOCK") = plane_score_block();
+  m.attr("PLANE_REFINE_BLOCK") = plane_refine_block();
   m.def("rigid_fit", &rigid_fit);
   m.attr("RIGID_FIT_REG_POINTS") = rigid_fit_reg_points();
   m.def("segmented_rigid_fit", &segmented_rigid_fit);

@@ -20,6 +20,9 @@ class SceneFlowDataset(Dataset):
     # flow_full (1,n,3)], the first cloud and its ground truth BEFORE
     # subsampling (dense-flow evaluation)
     return_full = False
+    # opt-in: loaders that strip the ground with a fixed rule (Kitti: y < -1.4)
+    # keep it, for users who segment the ground themselves (ops.fit_plane)
+    keep_ground = False
 
     def __init__(self, nb_points: int):
         super().__init__()

@@ -69,7 +69,8 @@ class Kitti(SceneFlowDataset):
         not_ground = np.logical_not(
             np.logical_and(sequence[0][:, 1] < GROUND_Y, sequence[1][:, 1] < GROUND_Y)
         )
-        sequence = [pc[not_ground] for pc in sequence]
+        if not self.keep_ground:
+            sequence = [pc[not_ground] for pc in sequence]
         is_close = np.logical_and(sequence[0][:, 2] < MAX_DEPTH, sequence[1][:, 2] < MAX_DEPTH)
         sequence = [pc[is_close] for pc in sequence]
         ground_truth = [np.ones_like(sequence[0][:, 0:1]), sequence[1] - sequence[0]]

@@ -17,8 +17,13 @@ from .batch import Batch
 
 class SyntheticSceneFlow(SceneFlowDataset):
     def __init__(self, nb_points: int, length: int = 256, seed: int = 0, extent: float = 10.0,
-                 full_points=None):
+                 full_points=None, ground_fraction: float = 0.0):
         super().__init__(nb_points)
+        if not 0.0 <= float(ground_fraction) < 1.0:
+            raise ValueError(f"ground_fraction must be in [0, 1), got {ground_fraction}")
+        # share of the points that lies on the plane y = -1.4 (2 cm noise)
+        # and follows the same rigid motion; 0 keeps the historical stream
+        self.ground_fraction = float(ground_fraction)
         self.length = length
         self.seed = seed
         self.extent = extent
@@ -38,7 +43,13 @@ class SyntheticSceneFlow(SceneFlowDataset):
         ang = rng.normal(0.0, 0.02)
         c, s = np.cos(ang, dtype=np.float32), np.sin(ang, dtype=np.float32)
         rot = np.array([[c, -s, 0], [s, c, 0], [0, 0, 1]], dtype=np.float32)
-        pc2 = pc1 @ rot.T + t + rng.normal(0.0, 0.01, size=(n, 3)).astype(np.float32)
+        noise = rng.normal(0.0, 0.01, size=(n, 3)).astype(np.float32)
+        if self.ground_fraction > 0:
+            # drawn after everything above: the default stream is untouched
+            k = int(round(self.ground_fraction * n))
+            sel = rng.permutation(n)[:k]
+            pc1[sel, 1] = (-1.4 + rng.normal(0.0, 0.02, size=k)).astype(np.float32)
+        pc2 = pc1 @ rot.T + t + noise
         ground_truth = [np.ones_like(pc1[:, 0:1]), pc2 - pc1]
         return [pc1, pc2], ground_truth
 

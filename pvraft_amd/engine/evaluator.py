@@ -31,6 +31,18 @@ that fit induces.  It reports the mean number of objects, the share of
 points in objects and objrigid_* metrics of the piecewise-rigid flow.  It
 uses --ego_thresh / --ego_iters for its ego fit and adds no ego_* keys
 unless --ego_motion is given as well.
+
+--ground_fit (beyond the reference as well) fits the ground plane of every
+sampled pc1 (ops.fit_plane, --ground_thresh, --ground_hyp, --ground_tilt,
+--ground_iters) after the forward, like --ego_motion.  It reports
+ground_ratio (share of points within the threshold of the plane),
+ground_below_ratio (share further below it), ground_tilt_deg (angle between
+the normal and +y), ground_height (height of the origin above the plane) and
+ng_* metrics: the usual ones with every ground point (on or below the plane)
+masked out through ground_truth[0].  --keep_ground makes the KITTI loader
+keep its y < -1.4 points; ground_iou then compares the fitted ground with
+that rule on pc1.  SYNTH puts 30 % of its points on a ground plane when the
+flag is on.  The sparse path and its metrics are untouched.
 """
 
 from __future__ import annotations
@@ -59,11 +71,15 @@ def build_eval_dataset(args):
         return FT3D(ddir, args.max_points, "test")
     if args.dataset == "KITTI":
         ddir = os.path.join(args.root, "data", "kitti_processed")
-        return Kitti(ddir, args.max_points)
+        ds = Kitti(ddir, args.max_points)
+        if getattr(args, "keep_ground", False):
+            ds.keep_ground = True
+        return ds
     if args.dataset == "SYNTH":
         full = 4 * args.max_points if getattr(args, "dense", False) else None
         return SyntheticSceneFlow(args.max_points, length=getattr(args, "synth_len", 32), seed=7,
-                                  full_points=full)
+                                  full_points=full,
+                                  ground_fraction=0.3 if getattr(args, "ground_fit", False) else 0.0)
     raise ValueError(f"Unknown dataset {args.dataset!r}")
 
 
@@ -86,7 +102,15 @@ def evaluate(args):
         max_objects=int(getattr(args, "obj_max_objects", 32)),
         iters=int(getattr(args, "obj_iters", 5)),
     )
-    if dense or ego or obj:
+    ground = bool(getattr(args, "ground_fit", False))
+    ground_kw = dict(
+        thresh=float(getattr(args, "ground_thresh", 0.2)),
+        hypotheses=int(getattr(args, "ground_hyp", 256)),
+        max_tilt_deg=float(getattr(args, "ground_tilt", 20.0)),
+        refine_iters=int(getattr(args, "ground_iters", 3)),
+    )
+    ground_iou = ground and args.dataset == "KITTI" and bool(getattr(args, "keep_ground", False))
+    if dense or ego or obj or ground:
         from pvraft_amd import ops
     if dense:
         dataset.return_full = True
@@ -120,6 +144,8 @@ def evaluate(args):
     dense_sums = [0.0] * 4
     ego_sums = [0.0] * 7
     obj_sums = [0.0] * 6
+    ground_sums = [0.0] * 9
+    n_ng = 0
     n = 0
     for batch in loader:
         batch = batch.to(device, non_blocking=True)
@@ -173,6 +199,29 @@ def evaluate(args):
             head = (om.num_objects.float().mean().item(), (om.labels >= 0).float().mean().item())
             for j, v in enumerate(head + tuple(objrigid_m)):
                 obj_sums[j] += v
+        if ground:
+            pc1 = batch["sequence"][0].float()
+            gfit = ops.fit_plane(pc1, **ground_kw)
+            gt_mask, gt_flow = batch["ground_truth"]
+            up = torch.tensor([0.0, 1.0, 0.0], device=pc1.device)
+            tilt = torch.rad2deg(torch.atan2(torch.linalg.cross(gfit.normal, up.expand_as(gfit.normal)).norm(dim=-1),
+                                             gfit.normal @ up)).mean().item()
+            iou = 0.0
+            if ground_iou:
+                from pvraft_amd.data.kitti import GROUND_Y
+
+                rule = pc1[..., 1] < GROUND_Y
+                union = (rule | gfit.ground).sum().item()
+                iou = (rule & gfit.ground).sum().item() / union if union else 1.0
+            head = (gfit.inlier.float().mean().item(), (gfit.ground & ~gfit.inlier).float().mean().item(), tilt,
+                    gfit.offset.mean().item(), iou)
+            ng_mask = gt_mask * (~gfit.ground).unsqueeze(-1).to(gt_mask.dtype)
+            ng_m = (0.0,) * 4
+            if ng_mask.sum().item() > 0:  # a sample that is all ground adds nothing to ng_*
+                ng_m = compute_epe(final.float(), {"ground_truth": [ng_mask, gt_flow]})
+                n_ng += 1
+            for j, v in enumerate(head + tuple(ng_m)):
+                ground_sums[j] += v
         if dump:
             import numpy as np
 
@@ -194,6 +243,10 @@ def evaluate(args):
                 np.save(os.path.join(d, "obj_R.npy"), om.R.cpu().numpy())
                 np.save(os.path.join(d, "obj_t.npy"), om.t.cpu().numpy())
                 np.save(os.path.join(d, "flow_objrigid.npy"), om.rigid_flow.cpu().numpy())
+            if ground:
+                np.save(os.path.join(d, "ground_mask.npy"), gfit.ground.cpu().numpy())
+                np.save(os.path.join(d, "ground_plane.npy"),
+                        torch.cat([gfit.normal, gfit.offset.unsqueeze(-1)], -1).cpu().numpy())
         n += 1
     means = [s / max(n, 1) for s in sums]
     log.info(
@@ -253,4 +306,24 @@ def evaluate(args):
             objrigid_acc3d_relax=omeans[4],
             objrigid_outlier=omeans[5],
         )
+    if ground:
+        gmeans = [v / max(n, 1) for v in ground_sums[:5]] + [v / max(n_ng, 1) for v in ground_sums[5:]]
+        log.info(
+            f"[test {args.dataset} ground thresh={ground_kw['thresh']} hyp={ground_kw['hypotheses']} "
+            f"tilt={ground_kw['max_tilt_deg']} iters={ground_kw['refine_iters']}] "
+            f"ratio={gmeans[0]:.4f} below={gmeans[1]:.4f} tilt={gmeans[2]:.3f}deg height={gmeans[3]:.3f} "
+            f"ng EPE3D={gmeans[5]:.4f} Acc3DS={gmeans[6]:.4f} Acc3DR={gmeans[7]:.4f} Outlier={gmeans[8]:.4f}"
+        )
+        results.update(
+            ground_ratio=gmeans[0],
+            ground_below_ratio=gmeans[1],
+            ground_tilt_deg=gmeans[2],
+            ground_height=gmeans[3],
+            ng_epe=gmeans[5],
+            ng_acc3d_strict=gmeans[6],
+            ng_acc3d_relax=gmeans[7],
+            ng_outlier=gmeans[8],
+        )
+        if ground_iou:
+            results["ground_iou"] = gmeans[4]
     return results

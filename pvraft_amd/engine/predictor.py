@@ -10,6 +10,8 @@ launch-collapse as the training step, applied to serving.
 
     # flow for every point of full-resolution clouds (batch-1 predictors):
     dense = pred.predict_dense(pc1_full, pc2_full, k=3)   # (n1, 3)
+    # ... of raw scans that still contain the ground:
+    dense = pred.predict_dense(pc1_full, pc2_full, remove_ground=True)
 
     # flow plus the ego-motion it implies and a static/dynamic split:
     flow, ego = pred.predict_ego_motion(xyz1, xyz2)       # ego.R, ego.t, ...
@@ -119,7 +121,8 @@ class Predictor:
     @torch.no_grad()
     def predict_dense(self, pc1_full: torch.Tensor, pc2_full: torch.Tensor, k: int = 3,
                       generator: Optional[torch.Generator] = None,
-                      return_sparse: bool = False):
+                      return_sparse: bool = False, remove_ground: bool = False,
+                      ground_kw: Optional[dict] = None):
         """Flow for EVERY point of ``pc1_full`` ((n1,3) or (1,n1,3)).
 
         Draws ``points`` indices without replacement from each full cloud
@@ -133,6 +136,18 @@ class Predictor:
         device; with ``return_sparse`` the tuple (flow, idx1, flow_sub):
         idx1 (points,) int64 indices into pc1_full and the sparse flow
         flow_sub (points, 3) predicted at them.
+
+        ``remove_ground=True`` is for raw scans that still contain the
+        ground (the network was trained on clouds without it): each full
+        cloud gets its own ``ops.fit_plane(cloud, **ground_kw)`` and the
+        samples are drawn, with the same ``randperm`` mechanics, only among
+        that cloud's non-ground points (``~fit.ground``: above the plane by
+        more than ``thresh``).  The dense flow still covers every point of
+        ``pc1_full``, ground included, and with ``return_sparse`` the tuple
+        gains a fourth entry, the (n1,) bool ground mask of ``pc1_full``.
+        Fewer than ``points`` non-ground points in a cloud raise ValueError.
+        Compacting the non-ground indices reads their count on the host:
+        one synchronisation per cloud, in this eager pre-phase only.
         """
         from pvraft_amd import ops
 
@@ -152,13 +167,28 @@ class Predictor:
             clouds.append(pc.to(self.device))
         gdev = generator.device if generator is not None else torch.device("cpu")
         subs, idxs = [], []
-        for pc in clouds:
-            idx = torch.randperm(pc.shape[0], generator=generator, device=gdev)[:points].to(self.device)
+        ground1 = None
+        for name, pc in zip(("pc1_full", "pc2_full"), clouds):
+            if remove_ground:
+                fit = ops.fit_plane(pc.float().unsqueeze(0), **(ground_kw or {}))
+                if ground1 is None:
+                    ground1 = fit.ground[0]
+                keep = (~fit.ground[0]).nonzero().squeeze(1)  # host sync: the count
+                if keep.numel() < points:
+                    raise ValueError(
+                        f"{name} has {keep.numel()} non-ground points, fewer than the {points} the predictor samples"
+                    )
+                sel = torch.randperm(keep.numel(), generator=generator, device=gdev)[:points].to(self.device)
+                idx = keep[sel]
+            else:
+                idx = torch.randperm(pc.shape[0], generator=generator, device=gdev)[:points].to(self.device)
             idxs.append(idx)
             subs.append(pc[idx].float().unsqueeze(0))
         flow_sub = self(subs[0], subs[1])  # (1, points, 3)
         dense, _, _ = ops.knn_interpolate(subs[0], flow_sub, clouds[0].float().unsqueeze(0), k)
         dense = dense[0].to(pc1_full.dtype)
         if return_sparse:
+            if remove_ground:
+                return dense, idxs[0], flow_sub[0], ground1
             return dense, idxs[0], flow_sub[0]
         return dense

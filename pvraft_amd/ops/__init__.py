@@ -1243,3 +1243,111 @@ def object_motion(
     rigid_flow = torch.where(ego.static.unsqueeze(-1), ego.rigid_flow, flow.to(R.dtype))
     rigid_flow = torch.where(in_obj.unsqueeze(-1), obj_flow, rigid_flow)
     return ObjectMotion(labels, num_objects, count, R, t, ok, residual, rigid_flow, ego)
+
+
+# ---------------------------------------------------------------------------
+# ground plane (csrc/plane_fit.hip)
+# ---------------------------------------------------------------------------
+
+
+class PlaneFit(NamedTuple):
+    """Result of ``fit_plane``: normal (B,3) unit, ``normal . up > 0``;
+    offset (B,), the plane is ``normal . p + offset = 0``; height (B,N) signed
+    distance above the plane (+INF for a non-finite point); ground (B,N) bool
+    ``height <= thresh``; inlier (B,N) bool ``|height| <= thresh``; count (B,)
+    int32 inlier count of the winning hypothesis; best (B,) int32 its index or
+    -1; rounds (B,) int32 accepted refinement rounds; ok (B,) bool."""
+
+    normal: Tensor
+    offset: Tensor
+    height: Tensor
+    ground: Tensor
+    inlier: Tensor
+    count: Tensor
+    best: Tensor
+    rounds: Tensor
+    ok: Tensor
+
+
+def _plane_inputs(name, xyz, mask):
+    if xyz.dim() != 3 or xyz.shape[-1] != 3:
+        raise ValueError(f"{name} needs xyz (B,N,3), got {tuple(xyz.shape)}")
+    if mask is not None:
+        if mask.shape != xyz.shape[:2]:
+            raise ValueError(f"{name} needs mask (B,N), got {tuple(mask.shape)}")
+        mask = mask.detach().bool().contiguous()
+    return xyz.detach().float().contiguous(), mask
+
+
+def plane_hypotheses(
+    xyz: Tensor, mask: Optional[Tensor] = None, thresh: float = 0.2, hypotheses: int = 256,
+    up=(0.0, 1.0, 0.0), max_tilt_deg: float = 20.0, seed: int = 0,
+) -> Tuple[Tensor, Tensor]:
+    """Stages A and B of ``fit_plane`` alone, for tests and debugging: the
+    drawn point triples idx (B,H,3) int32 and their exact inlier counts
+    count (B,H) int32; an invalid hypothesis has idx = -1 and count = -1.
+    The same integers on every backend."""
+    thresh, thresh2, cos2, up32, H, _, seed = reference.plane_params(thresh, hypotheses, up, max_tilt_deg, 0, seed)
+    xyz, mask = _plane_inputs("plane_hypotheses", xyz, mask)
+    B, N = xyz.shape[:2]
+    if _use_hip(xyz) and B > 0 and N > 0:
+        idx, count = _EXT.plane_fit(xyz, mask, thresh, thresh2, cos2, up32[0], up32[1], up32[2], H, -1, seed)
+        return idx, count
+    return reference.plane_hypotheses(xyz, mask, thresh2, cos2, up32, H, seed)
+
+
+def fit_plane(
+    xyz: Tensor, mask: Optional[Tensor] = None, thresh: float = 0.2, hypotheses: int = 256,
+    up=(0.0, 1.0, 0.0), max_tilt_deg: float = 20.0, refine_iters: int = 3, seed: int = 0,
+) -> PlaneFit:
+    """Robust ground-plane fit of a cloud: xyz (B,N,3), optional mask (B,N)
+    bool -> ``PlaneFit``.  1 <= hypotheses <= 4096, 0 <= refine_iters <= 16,
+    0 < max_tilt_deg < 90, thresh > 0, ``up`` non-zero and finite; anything
+    else raises ValueError.
+
+    ``mask`` restricts which points FIT the plane (a point is eligible if it
+    is masked in and its three coordinates are finite); every finite point
+    still gets a height and its labels.  A point with a non-finite
+    coordinate is never drawn and reports height +INF, both labels False.
+
+    A. ``hypotheses`` planes through seeded point triples.  With unsigned
+       32-bit arithmetic
+         mix(x): x ^= x>>16; x *= 0x85EBCA6B; x ^= x>>13; x *= 0xC2B2AE35; x ^= x>>16
+         key(b) = mix(seed ^ mix(b*0x9E3779B1 + 1))
+         draw(b,h,j,t) = mix(key(b) ^ ((h*3 + j)*8 + t)) mod N
+       slot j of hypothesis h takes the first of its 8 draws that is
+       eligible.  n = (p1 - p0) x (p2 - p0) in fp32, every operation rounded
+       on its own.  The hypothesis is invalid if a slot stays empty, two
+       slots coincide, |n|^2 is zero or non-finite, or n is tilted more than
+       ``max_tilt_deg`` away from ``up``: (n.up)^2 < cos^2(max_tilt) |n|^2.
+    B. count[b,h] = number of eligible points with (n.(p - p0))^2 <=
+       thresh^2 |n|^2, in the same fp32 rules: an exact integer.  The largest
+       count wins, ties go to the smallest h.
+    C. ``refine_iters`` rounds of reweighted least squares with the Tukey
+       biweight w = (1 - (height/thresh)^2)^2 inside |height| < thresh: fp64
+       sums over points centred on the winner's p0, the new normal is the
+       eigenvector of the smallest eigenvalue of the weighted covariance,
+       the new offset puts the weighted centroid on the plane.  A round is
+       rejected (and the loop ends with the previous plane) when fewer than
+       3 points carry weight, the two smallest eigenvalues are not separated
+       (a collinear set) or the new normal violates the tilt limit.
+    D. height = normal . p + offset evaluated in fp64, rounded to fp32.
+
+    ``ok`` is False when no hypothesis is valid (fewer than 3 eligible
+    points, only vertical structure, ...): then normal = up, offset = 0, all
+    heights +INF, count = 0, best = -1, rounds = 0.
+
+    GPU: four launches (csrc/plane_fit.hip), no host synchronisation,
+    bit-reproducible run to run.  Not differentiable.  bf16/fp16/fp64 or
+    non-contiguous inputs are converted to contiguous fp32 here.
+
+    The defaults (0.2 m, 256 hypotheses, 20 degrees, 3 rounds) are untuned
+    guesses at metric driving scenes with y up.
+    """
+    thresh, thresh2, cos2, up32, H, iters, seed = reference.plane_params(
+        thresh, hypotheses, up, max_tilt_deg, refine_iters, seed)
+    xyz, mask = _plane_inputs("fit_plane", xyz, mask)
+    B, N = xyz.shape[:2]
+    if _use_hip(xyz) and B > 0 and N > 0:
+        return PlaneFit(*_EXT.plane_fit(xyz, mask, thresh, thresh2, cos2, up32[0], up32[1], up32[2], H, iters, seed))
+    return PlaneFit(*reference.fit_plane(xyz, mask, thresh, thresh2, cos2, up32, H, iters, seed))

@@ -507,3 +507,193 @@ def segmented_rigid_fit(
             return (torch.zeros(B, 0, 3, 3, dtype=dt, device=dev), torch.zeros(B, 0, 3, dtype=dt, device=dev),
                     residual, torch.zeros(B, 0, dtype=torch.bool, device=dev))
         return torch.stack(Rs, 1), torch.stack(ts, 1), residual, torch.stack(oks, 1)
+
+
+# ---------------------------------------------------------------------------
+# Ground plane (absent in the reference): seeded RANSAC + Tukey refinement
+# ---------------------------------------------------------------------------
+
+PLANE_GAP = 1e-9  # eigenvalue separation of an accepted refit, relative to the largest
+
+
+def _f32(v: float) -> float:
+    return float(torch.tensor(float(v), dtype=torch.float64).to(torch.float32).item())
+
+
+def plane_params(thresh, hypotheses, up, max_tilt_deg, refine_iters, seed):
+    """Checks the scalar arguments of ``fit_plane`` and returns the numbers
+    every backend computes with: ``up`` normalised in double and rounded to
+    fp32, ``cos2 = fp32(cos^2 max_tilt)``, ``thresh2 = fp32(thresh^2)`` and
+    the seed as an unsigned 32-bit integer.  Raises ValueError."""
+    try:
+        thresh, max_tilt_deg = float(thresh), float(max_tilt_deg)
+        up = tuple(float(v) for v in up)
+        hypotheses, refine_iters, seed = int(hypotheses), int(refine_iters), int(seed)
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"fit_plane: bad argument: {e}") from None
+    if not (thresh > 0 and math.isfinite(thresh)):
+        raise ValueError(f"fit_plane requires a finite thresh > 0, got {thresh}")
+    if not 1 <= hypotheses <= 4096:
+        raise ValueError(f"fit_plane requires 1 <= hypotheses <= 4096, got {hypotheses}")
+    if not 0 <= refine_iters <= 16:
+        raise ValueError(f"fit_plane requires 0 <= refine_iters <= 16, got {refine_iters}")
+    if not 0 < max_tilt_deg < 90:
+        raise ValueError(f"fit_plane requires 0 < max_tilt_deg < 90, got {max_tilt_deg}")
+    if len(up) != 3 or not all(math.isfinite(v) for v in up):
+        raise ValueError(f"fit_plane requires a finite 3-vector up, got {up}")
+    scale = max(abs(v) for v in up)
+    if not scale > 0:
+        raise ValueError("fit_plane requires a non-zero up")
+    un = [v / scale for v in up]
+    norm = math.sqrt(sum(v * v for v in un))
+    up32 = tuple(_f32(v / norm) for v in un)
+    cos2 = _f32(math.cos(math.radians(max_tilt_deg)) ** 2)
+    thresh2 = _f32(thresh * thresh)
+    if not (thresh2 > 0 and math.isfinite(thresh2)):
+        raise ValueError(f"fit_plane: thresh^2 is not a positive fp32 number for thresh = {thresh}")
+    return thresh, thresh2, cos2, up32, hypotheses, refine_iters, seed & 0xFFFFFFFF
+
+
+def _mul32(x: Tensor, c: int) -> Tensor:
+    # (x * c) mod 2^32 on int64 tensors holding uint32 values, without
+    # leaving the int64 range
+    lo = x * (c & 0xFFFF)
+    hi = ((x * (c >> 16)) & 0xFFFF) << 16
+    return (lo + hi) & 0xFFFFFFFF
+
+
+def _mix32(x: Tensor) -> Tensor:
+    x = x ^ (x >> 16)
+    x = _mul32(x, 0x85EBCA6B)
+    x = x ^ (x >> 13)
+    x = _mul32(x, 0xC2B2AE35)
+    return x ^ (x >> 16)
+
+
+def _plane_stage_ab(xyz: Tensor, mask: Optional[Tensor], thresh2: float, cos2: float, up32, H: int, seed: int):
+    """Stages A and B on fp32 ``xyz``: idx (B,H,3) int32, count (B,H) int32,
+    the fp32 normals n (B,H,3), pivots p0 (B,H,3) and n.up (B,H)."""
+    B, N, _ = xyz.shape
+    dev = xyz.device
+    i64 = dict(dtype=torch.int64, device=dev)
+    elig = torch.isfinite(xyz).all(-1)
+    if mask is not None:
+        elig = elig & mask
+    b = torch.arange(B, **i64)
+    key = _mix32(seed ^ _mix32((_mul32(b, 0x9E3779B1) + 1) & 0xFFFFFFFF))  # (B,)
+    ctr = torch.arange(H * 3 * 8, **i64).view(1, H, 3, 8)
+    cand = _mix32(key.view(B, 1, 1, 1) ^ ctr) % N  # (B,H,3,8)
+    ce = elig.gather(1, cand.view(B, -1)).view(B, H, 3, 8)
+    first = ce.int().argmax(-1, keepdim=True)  # first eligible try
+    idx = cand.gather(-1, first).squeeze(-1)  # (B,H,3)
+    valid = ce.any(-1).all(-1)
+    valid = valid & (idx[..., 0] != idx[..., 1]) & (idx[..., 0] != idx[..., 2]) & (idx[..., 1] != idx[..., 2])
+    idx = torch.where(valid.unsqueeze(-1), idx, torch.zeros_like(idx))
+    pts = xyz.gather(1, idx.view(B, H * 3, 1).expand(B, H * 3, 3)).view(B, H, 3, 3)
+    p0 = pts[:, :, 0]
+    u = pts[:, :, 1] - p0
+    v = pts[:, :, 2] - p0
+    nx = (u[..., 1] * v[..., 2]) - (u[..., 2] * v[..., 1])
+    ny = (u[..., 2] * v[..., 0]) - (u[..., 0] * v[..., 2])
+    nz = (u[..., 0] * v[..., 1]) - (u[..., 1] * v[..., 0])
+    nn = (nx * nx + ny * ny) + nz * nz
+    nu = (nx * up32[0] + ny * up32[1]) + nz * up32[2]
+    c2 = torch.tensor(cos2, dtype=torch.float32, device=dev)
+    t2 = torch.tensor(thresh2, dtype=torch.float32, device=dev) * nn
+    valid = valid & torch.isfinite(nn) & (nn > 0) & (nu * nu >= c2 * nn)
+    n = torch.stack([nx, ny, nz], -1)
+
+    nan = torch.full((), float("nan"), dtype=torch.float32, device=dev)
+    x = torch.where(elig, xyz[..., 0], nan).unsqueeze(1)  # ineligible: every comparison fails
+    y = xyz[..., 1].unsqueeze(1)
+    z = xyz[..., 2].unsqueeze(1)
+    count = torch.empty(B, H, **i64)
+    hc = max(1, (1 << 20) // max(N * B, 1))  # (B,hc,N) fp32 temporaries of <= 4 MB
+    for s in range(0, H, hc):
+        sl = slice(s, s + hc)
+        e = ((x - p0[:, sl, 0:1]) * nx[:, sl, None] + (y - p0[:, sl, 1:2]) * ny[:, sl, None]) \
+            + (z - p0[:, sl, 2:3]) * nz[:, sl, None]
+        count[:, sl] = (e * e <= t2[:, sl, None]).sum(-1)
+    count = torch.where(valid, count, torch.full_like(count, -1)).int()
+    idx = torch.where(valid.unsqueeze(-1), idx, torch.full_like(idx, -1)).int()
+    return idx, count, n, p0, nu
+
+
+def plane_hypotheses(xyz, mask, thresh2, cos2, up32, hypotheses, seed):
+    """Stages A and B of ``fit_plane`` (see ``ops.fit_plane``): idx (B,H,3)
+    int32 and count (B,H) int32, -1 for an invalid hypothesis."""
+    with torch.no_grad():
+        B, N, _ = xyz.shape
+        if N == 0:
+            return (torch.full((B, hypotheses, 3), -1, dtype=torch.int32, device=xyz.device),
+                    torch.full((B, hypotheses), -1, dtype=torch.int32, device=xyz.device))
+        idx, count, _, _, _ = _plane_stage_ab(xyz.float(), mask, thresh2, cos2, up32, hypotheses, seed)
+        return idx, count
+
+
+def fit_plane(xyz, mask, thresh, thresh2, cos2, up32, hypotheses, refine_iters, seed):
+    """Torch version of ``ops.fit_plane`` with the prepared numbers of
+    ``plane_params``: stages A and B in fp32 elementwise operations (the
+    same integers as every other backend), the refinement sums, the 3x3
+    eigenproblem (``torch.linalg.eigh``) and the heights in fp64.  Returns
+    the nine fields of ``ops.PlaneFit``."""
+    with torch.no_grad():
+        B, N, _ = xyz.shape
+        dev = xyz.device
+        f64 = dict(dtype=torch.float64, device=dev)
+        up = torch.tensor(up32, **f64)
+        normal = up.expand(B, 3).clone()
+        offset = torch.zeros(B, **f64)
+        height = torch.full((B, N), float("inf"), **f64)
+        cnt = torch.zeros(B, dtype=torch.int32, device=dev)
+        best = torch.full((B,), -1, dtype=torch.int32, device=dev)
+        rounds = torch.zeros(B, dtype=torch.int32, device=dev)
+        ok = torch.zeros(B, dtype=torch.bool, device=dev)
+        if N > 0:
+            x32 = xyz.float()
+            _, count, n, p0, nu = _plane_stage_ab(x32, mask, thresh2, cos2, up32, hypotheses, seed)
+            cmax = count.max(1).values
+            first = (count == cmax.unsqueeze(1)).int().argmax(1)  # the first maximum: ties go to the smallest h
+            ok = cmax >= 0
+            best = torch.where(ok, first, torch.full_like(first, -1)).int()
+            cnt = torch.where(ok, cmax, torch.zeros_like(cmax)).int()
+            sel = first.view(B, 1, 1).expand(B, 1, 3)
+            nb = n.gather(1, sel).squeeze(1).double()
+            pv = p0.gather(1, sel).squeeze(1).double()  # pivot
+            sg = torch.where(nu.gather(1, first.view(B, 1)).squeeze(1) < 0, -1.0, 1.0).double()
+            nrm = nb.norm(dim=-1).clamp_min(1e-300)
+            nd = torch.where(ok.unsqueeze(-1), nb * (sg / nrm).unsqueeze(-1), up.expand(B, 3))
+            dp = torch.zeros(B, **f64)
+            fin = torch.isfinite(x32).all(-1)
+            elig = fin if mask is None else fin & mask
+            q = torch.where(fin.unsqueeze(-1), x32.double() - pv.unsqueeze(1), torch.zeros((), **f64))
+            alive = ok.clone()
+            for _ in range(refine_iters):
+                h = (q * nd.unsqueeze(1)).sum(-1) + dp.unsqueeze(1)
+                w = (1 - (h / thresh) ** 2) ** 2
+                w = torch.where(elig & (h.abs() < thresh), w, torch.zeros((), **f64))
+                W = w.sum(1)
+                nw = (w > 0).sum(1)
+                c = (w.unsqueeze(-1) * q).sum(1) / W.clamp_min(1e-300).unsqueeze(-1)
+                qc = q - c.unsqueeze(1)
+                C = torch.einsum("bn,bni,bnj->bij", w, qc, qc)
+                good = alive & (nw >= 3) & (W > 0) & torch.isfinite(C).all(-1).all(-1)
+                lam, vec = torch.linalg.eigh(torch.where(good.view(B, 1, 1), C, torch.eye(3, **f64).expand(B, 3, 3)))
+                m = vec[:, :, 0]
+                d = (m * up).sum(-1)
+                m = m * torch.where(d < 0, -1.0, 1.0).double().unsqueeze(-1)
+                d = (m * up).sum(-1)
+                good = good & ((lam[:, 1] - lam[:, 0]) > PLANE_GAP * lam[:, 2]) & (d * d >= cos2)
+                nd = torch.where(good.unsqueeze(-1), m, nd)
+                dp = torch.where(good, -(m * c).sum(-1), dp)
+                rounds = rounds + good.int()
+                alive = good  # a rejected round would be rejected again: the plane did not move
+            h = (q * nd.unsqueeze(1)).sum(-1) + dp.unsqueeze(1)
+            height = torch.where(fin & ok.unsqueeze(1), h, torch.full_like(h, float("inf")))
+            normal = nd
+            offset = torch.where(ok, dp - (nd * pv).sum(-1), torch.zeros_like(dp))
+        height = height.float()
+        height = torch.where(torch.isfinite(height), height, torch.full_like(height, float("inf")))
+        th32 = torch.tensor(thresh, dtype=torch.float32, device=dev)
+        return (normal.float(), offset.float(), height, height <= th32, height.abs() <= th32,
+                cnt, best, rounds.int(), ok)

@@ -37,6 +37,7 @@ SOURCES = [
     "pvraft_amd/csrc/flow_smooth.hip",
     "pvraft_amd/csrc/rigid_fit.hip",
     "pvraft_amd/csrc/cluster.hip",
+    "pvraft_amd/csrc/plane_fit.hip",
 ]
 
 setup(

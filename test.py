@@ -29,6 +29,12 @@ def parse_args():
     parser.add_argument("--obj_min_points", help="smallest object, in points", default=8, type=int)
     parser.add_argument("--obj_max_objects", help="objects kept per sample, largest first", default=32, type=int)
     parser.add_argument("--obj_iters", help="reweighting rounds of the per-object fits", default=5, type=int)
+    parser.add_argument("--ground_fit", help="also fit the ground plane of every pc1 and report ground_* / ng_* metrics", action="store_true")
+    parser.add_argument("--ground_thresh", help="point-to-plane distance of a ground point (m)", default=0.2, type=float)
+    parser.add_argument("--ground_hyp", help="plane hypotheses of the ground fit", default=256, type=int)
+    parser.add_argument("--ground_tilt", help="largest angle between the ground normal and +y (degrees)", default=20.0, type=float)
+    parser.add_argument("--ground_iters", help="refinement rounds of the ground fit", default=3, type=int)
+    parser.add_argument("--keep_ground", help="KITTI: keep the y < -1.4 points the loader removes by default", action="store_true")
     return parser.parse_args()
 
 
