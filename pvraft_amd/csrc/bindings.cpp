@@ -3,6 +3,10 @@
 #include <ATen/hip/HIPContext.h>
 #include <hip/hip_runtime.h>
 
+#include <map>
+#include <string>
+#include <utility>
+
 void launch_knn_graph(const float*, int*, int, int, int, hipStream_t);
 void launch_knn_csr(const int*, int*, int*, int*, int*, int*, unsigned char*,
                     int, int, int, hipStream_t);
@@ -129,11 +133,14 @@ void launch_kg_fwd(const float*, const float*, const float*, float*, float*,
                    float*, unsigned char*, unsigned char*, void*,
                    unsigned char*, float*, int, long, int, int, int, float,
                    const float*, bool, int, bool, hipStream_t);
-void launch_kg_bwd(const void*, const float*, const float*, const float*,
-                   const unsigned char*, const float*, const float*,
-                   const float*, const float*, const float*, float*, float*,
-                   float*, float*, float*, float*, int, long, int, int, int,
-                   const float*, bool, int, hipStream_t);
+void launch_kg_bwd(const void*, bool, const float*, const float*,
+                   const float*, const unsigned char*, const float*,
+                   const float*, const float*, const float*, const float*,
+                   float*, float*, double*, float*, unsigned char*, float*,
+                   float*, float*, float*, float*, float*, bool, int, long,
+                   int, int, int, float, const float*, bool, hipStream_t);
+long kg_bwd_part_len(int, long, int, int);
+long kg_bwd_pgrad_len(int, int);
 void launch_gnmp_bwd(const void*, const void*, const unsigned char*,
                      const float*, const float*, const float*, const float*,
                      float*, float*, float*, float*, int, void*, int, long,
@@ -188,6 +195,21 @@ torch::Tensor& persistent_ws(long len, const torch::TensorOptions& opt) {
   auto it = cache->find(len);
   if (it == cache->end())
     it = cache->emplace(len, torch::zeros({len}, opt)).first;
+  return it->second;
+}
+
+// persistent_ws is keyed by length alone, so two workspaces of equal
+// length are the same tensor.  An op that holds several workspaces at once
+// names each one's role; a role's buffers never alias another role's or a
+// plain persistent_ws buffer.  Contents are unspecified between calls.
+torch::Tensor& persistent_ws_role(const char* role, long len,
+                                  const torch::TensorOptions& opt) {
+  static auto* cache =
+      new std::map<std::pair<std::string, long>, torch::Tensor>();
+  const auto key = std::make_pair(std::string(role), len);
+  auto it = cache->find(key);
+  if (it == cache->end())
+    it = cache->emplace(key, torch::zeros({len}, opt)).first;
   return it->second;
 }
 
@@ -762,54 +784,104 @@ std::vector<torch::Tensor> knn_gnmp_fwd(torch::Tensor raw, torch::Tensor W,
   return {y, am, vsel, mean, rstd};
 }
 
+// dy: the pooled gradient in the layout it arrives in, (B, C, N) when
+// dy_channel_major else (B, N, C).  With the five accumulate targets (the
+// parameters' fp32 grad buffers) the parameter gradients are added into
+// them in-stream and only {draw} is returned; without, {draw, dW, dcb,
+// dgamma, dbeta, dslope}.
 std::vector<torch::Tensor> knn_gnmp_bwd(
-    torch::Tensor dyT, torch::Tensor raw, torch::Tensor W, torch::Tensor cb,
+    torch::Tensor dy, torch::Tensor raw, torch::Tensor W, torch::Tensor cb,
     torch::Tensor am, torch::Tensor vsel, torch::Tensor mean,
     torch::Tensor rstd, int64_t G, torch::Tensor gamma, torch::Tensor beta,
-    torch::Tensor slope_t) {
-  TORCH_CHECK(dyT.is_cuda() && dyT.is_contiguous() && dyT.dim() == 3,
-              "dyT must be contiguous (B,N,C)");
+    torch::Tensor slope_t, double eps, bool dy_channel_major = false,
+    c10::optional<torch::Tensor> wtarget = c10::nullopt,
+    c10::optional<torch::Tensor> cbtarget = c10::nullopt,
+    c10::optional<torch::Tensor> gtarget = c10::nullopt,
+    c10::optional<torch::Tensor> btarget = c10::nullopt,
+    c10::optional<torch::Tensor> starget = c10::nullopt) {
   check_f32(raw, "raw");
+  check_f32(W, "W");
+  check_f32(cb, "cb");
+  check_f32(vsel, "vsel");
+  check_f32(gamma, "gamma");
+  check_f32(beta, "beta");
+  TORCH_CHECK(raw.dim() == 4 && raw.size(1) == 4, "raw must be (B,4,K,N)");
   const int B = raw.size(0), K = raw.size(2);
   const long N = raw.size(3);
   const int C = W.size(0);
-  const bool bf16 = dyT.scalar_type() == torch::kBFloat16;
+  TORCH_CHECK(C % 16 == 0 && C <= 128 && G >= 1 && C % G == 0 &&
+                  C / G >= 4 && K >= 1 && K <= 255 && N >= 1,
+              "knn_gnmp_bwd: need C % 16 == 0, C <= 128, C/G >= 4, "
+              "1 <= K <= 255");
+  TORCH_CHECK(dy.is_cuda() && dy.is_contiguous() && dy.dim() == 3 &&
+                  dy.size(0) == B &&
+                  dy.size(1) == (dy_channel_major ? (long)C : N) &&
+                  dy.size(2) == (dy_channel_major ? N : (long)C),
+              "dy must be contiguous (B,C,N) or (B,N,C) as flagged");
+  const bool bf16 = dy.scalar_type() == torch::kBFloat16;
+  TORCH_CHECK(bf16 || dy.scalar_type() == torch::kFloat32, "fp32/bf16 only");
+  TORCH_CHECK(am.is_contiguous() && am.scalar_type() == torch::kUInt8 &&
+                  am.numel() == (long)B * N * C && vsel.numel() == am.numel(),
+              "am/vsel must be (B,N,C)");
+  TORCH_CHECK(mean.numel() == B * G && rstd.numel() == B * G &&
+                  slope_t.numel() == 1,
+              "mean/rstd/slope shape mismatch");
   auto fopt = raw.options();
-  const int rows = B * (int)G;
-  int nblk = (int)((N + 255) / 256);
-  if (nblk < 1) nblk = 1;
-  const long n_out = (long)rows * 2 + C * 2 + 1;
-  // transient call-internal workspaces: persistent (see knn_gnmp_fwd).
-  // draw (the returned gradient) and ws2 (dW/dcb grad views) stay
-  // per-call: autograd's execution order gives no cross-node liveness
-  // guarantee for returned gradients.
-  auto scratch = persistent_ws(n_out * nblk * B, fopt)
-                     .view({n_out, (long)nblk * B});
-  auto ws = persistent_ws(n_out, fopt);
-  const int chunks_b = C / 8;
-  auto wscratch =
-      persistent_ws((long)C * 5 * nblk * chunks_b * 4 * B, fopt)
-          .view({(long)C * 5, (long)nblk * chunks_b * 4 * B});
-  auto ws2 = torch::empty({(long)C * 5}, fopt);
-  auto draw_part =
-      persistent_ws((long)chunks_b * B * 4 * K * N, fopt)
-          .view({(long)chunks_b, B, 4, K, N});
+  // transient call-internal workspaces: persistent (see knn_gnmp_fwd), one
+  // role each so no two of them alias at any shape.  Every element read is
+  // written earlier in the same call, so none needs zeroing.  draw (the
+  // returned gradient) and the fresh parameter gradients stay per-call:
+  // autograd's execution order gives no cross-node liveness guarantee for
+  // returned gradients.
+  const long bcn = (long)B * C * N;
+  auto part = persistent_ws_role("kg_bwd_part", kg_bwd_part_len(B, N, C, G),
+                                 fopt);
+  auto coef = persistent_ws_role("kg_bwd_coef", (long)B * 20, fopt);
+  auto pgrad = persistent_ws_role("kg_bwd_pgrad", kg_bwd_pgrad_len(B, C), fopt);
+  auto gsT = persistent_ws_role("kg_bwd_gs", bcn, fopt);
+  auto amT = persistent_ws_role("kg_bwd_am", (bcn + 3) / 4, fopt);
   auto draw = torch::empty({B, 4, K, N}, fopt);
-  launch_kg_bwd(dyT.data_ptr(), raw.data_ptr<float>(), W.data_ptr<float>(),
-                cb.data_ptr<float>(), am.data_ptr<unsigned char>(),
-                vsel.data_ptr<float>(), mean.data_ptr<float>(),
-                rstd.data_ptr<float>(), gamma.data_ptr<float>(),
-                beta.data_ptr<float>(), scratch.data_ptr<float>(),
-                ws.data_ptr<float>(), wscratch.data_ptr<float>(),
-                ws2.data_ptr<float>(), draw_part.data_ptr<float>(),
-                draw.data_ptr<float>(), B, N, K, C, (int)G,
-                slope_t.data_ptr<float>(), bf16, nblk, stream());
-  auto tail = gn_grads_finish(ws, draw, rows, C, fopt, c10::nullopt,
-                              c10::nullopt, c10::nullopt);
-  auto dW = ws2.narrow(0, 0, (long)C * 4).view({C, 4});
-  auto dcb = ws2.narrow(0, (long)C * 4, C);
-  // tail = {draw, dgamma, dbeta, dslope}
-  return {draw, dW, dcb, tail[1], tail[2], tail[3]};
+  const bool acc = wtarget.has_value();
+  torch::Tensor dW, dcb, dgamma, dbeta, dslope;
+  if (acc) {
+    TORCH_CHECK(cbtarget.has_value() && gtarget.has_value() &&
+                    btarget.has_value() && starget.has_value(),
+                "knn_gnmp_bwd: all five accumulate targets or none");
+    dW = *wtarget;
+    dcb = *cbtarget;
+    dgamma = *gtarget;
+    dbeta = *btarget;
+    dslope = *starget;
+    check_f32(dW, "wtarget");
+    check_f32(dcb, "cbtarget");
+    check_f32(dgamma, "gtarget");
+    check_f32(dbeta, "btarget");
+    check_f32(dslope, "starget");
+    TORCH_CHECK(dW.numel() == (long)C * 4 && dcb.numel() == C &&
+                    dgamma.numel() == C && dbeta.numel() == C &&
+                    dslope.numel() == 1,
+                "knn_gnmp_bwd: accumulate target sizes");
+  } else {
+    dW = torch::empty({C, 4}, fopt);
+    dcb = torch::empty({C}, fopt);
+    dgamma = torch::empty({C}, fopt);
+    dbeta = torch::empty({C}, fopt);
+    dslope = torch::empty({1}, fopt);
+  }
+  launch_kg_bwd(dy.data_ptr(), dy_channel_major, raw.data_ptr<float>(),
+                W.data_ptr<float>(), cb.data_ptr<float>(),
+                am.data_ptr<unsigned char>(), vsel.data_ptr<float>(),
+                mean.data_ptr<float>(), rstd.data_ptr<float>(),
+                gamma.data_ptr<float>(), beta.data_ptr<float>(),
+                part.data_ptr<float>(), coef.data_ptr<float>(),
+                (double*)pgrad.data_ptr<float>(), gsT.data_ptr<float>(), (unsigned char*)amT.data_ptr<float>(),
+                draw.data_ptr<float>(), dW.data_ptr<float>(),
+                dcb.data_ptr<float>(), dgamma.data_ptr<float>(),
+                dbeta.data_ptr<float>(), dslope.data_ptr<float>(), acc, B, N,
+                K, C, (int)G, (float)eps, slope_t.data_ptr<float>(), bf16,
+                stream());
+  if (acc) return {draw};
+  return {draw, dW, dcb, dgamma, dbeta, dslope};
 }
 
 // Capture-safe batched fp32->bf16 mirror refresh (csrc/cast_pack.hip):
@@ -1649,7 +1721,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("gamma"), pybind11::arg("beta"), pybind11::arg("eps"),
         pybind11::arg("slope_t"), pybind11::arg("out_bf16"),
         pybind11::arg("channel_major_out") = false);
-  m.def("knn_gnmp_bwd", &knn_gnmp_bwd);
+  m.def("knn_gnmp_bwd", &knn_gnmp_bwd, pybind11::arg("dy"),
+        pybind11::arg("raw"), pybind11::arg("W"), pybind11::arg("cb"),
+        pybind11::arg("am"), pybind11::arg("vsel"), pybind11::arg("mean"),
+        pybind11::arg("rstd"), pybind11::arg("G"), pybind11::arg("gamma"),
+        pybind11::arg("beta"), pybind11::arg("slope_t"), pybind11::arg("eps"),
+        pybind11::arg("dy_channel_major") = false,
+        pybind11::arg("wtarget") = pybind11::none(),
+        pybind11::arg("cbtarget") = pybind11::none(),
+        pybind11::arg("gtarget") = pybind11::none(),
+        pybind11::arg("btarget") = pybind11::none(),
+        pybind11::arg("starget") = pybind11::none());
   m.def("knn_graph", &knn_graph, "fused kNN graph (CDNA4)");
   m.def("knn_csr", &knn_csr, "inverse kNN adjacency as CSR (counting sort)");
   m.def("knn_interp_fwd", &knn_interp_fwd);

@@ -424,7 +424,7 @@ class _KnnGNMP(torch.autograd.Function):
             raw, w, cb, num_groups, ga, be, eps, st, out_bf16,
             channel_major_out)
         ctx.save_for_backward(raw, w, cb, am, vsel, mean, rstd, ga, be, st)
-        ctx.conf = (num_groups, weight.shape, weight.dtype)
+        ctx.conf = (num_groups, weight.shape, weight.dtype, eps)
         ctx.channel_major_out = channel_major_out
         ctx.param_refs = (weight, cbias, gamma, beta, slope_t)
         return y
@@ -434,13 +434,11 @@ class _KnnGNMP(torch.autograd.Function):
         from pvraft_amd.model import pointwise
 
         raw, w, cb, am, vsel, mean, rstd, ga, be, st = ctx.saved_tensors
-        num_groups, wshape, wdtype = ctx.conf
+        num_groups, wshape, wdtype, eps = ctx.conf
+        # the kernels read dy in the layout it arrives in: (B, C, N) for
+        # the channel-major output, (B, N, C) otherwise
         dy = dy.contiguous()
-        if ctx.channel_major_out:
-            dy = _EXT.batched_transpose(dy)  # kernels read dy point-major
-        draw, dW, dcb, dgamma, dbeta, dslope = _EXT.knn_gnmp_bwd(
-            dy, raw, w, cb, am, vsel, mean, rstd, num_groups,
-            ga, be, st)
+        cm = ctx.channel_major_out
         params = ctx.param_refs
         if pointwise._DEFER.on and all(
             p.is_leaf and p.requires_grad for p in params
@@ -452,13 +450,23 @@ class _KnnGNMP(torch.autograd.Function):
             # they are written -- measured 1e13-garbage conv grads,
             # scripts/graph_step_gradcheck.py); every other weight grad
             # already rides the deferred/drain path for the same reason.
-            wt, cbt, gat, bet, slt = params
-            pointwise._grad_buffer(wt).view(-1).add_(dW.view(-1))
-            pointwise._grad_buffer(cbt).add_(dcb)
-            pointwise._grad_buffer(gat).add_(dgamma)
-            pointwise._grad_buffer(bet).add_(dbeta)
-            pointwise._grad_buffer(slt).view(-1).add_(dslope)
+            bufs = [pointwise._grad_buffer(p) for p in params]
+            if all(t.dtype == torch.float32 and t.is_contiguous()
+                   for t in bufs):
+                # the coefficient kernel adds into the buffers itself
+                (draw,) = _EXT.knn_gnmp_bwd(
+                    dy, raw, w, cb, am, vsel, mean, rstd, num_groups, ga,
+                    be, st, eps, cm, *[t.view(-1) for t in bufs])
+            else:
+                draw, *grads = _EXT.knn_gnmp_bwd(
+                    dy, raw, w, cb, am, vsel, mean, rstd, num_groups, ga,
+                    be, st, eps, cm)
+                for t, g in zip(bufs, grads):
+                    t.view(-1).add_(g.view(-1))
             return (draw, None, None, None, None, None, None, None, None)
+        draw, dW, dcb, dgamma, dbeta, dslope = _EXT.knn_gnmp_bwd(
+            dy, raw, w, cb, am, vsel, mean, rstd, num_groups, ga, be, st, eps,
+            cm)
         return (draw, dW.view(wshape).to(wdtype), dcb, None, dgamma, dbeta,
                 None, dslope.reshape(1), None)
 
