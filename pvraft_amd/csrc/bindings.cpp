@@ -116,14 +116,14 @@ void launch_egnmp_fwd(const void*, const int*, float*, float*, float*,
                       unsigned char*, unsigned char*, float*, void*,
                       unsigned char*, float*,
                       int, long, int, int, int, float, int, float,
-                      const float*, bool, int, bool, hipStream_t);
+                      const float*, bool, int, bool, bool, hipStream_t);
 void launch_egnmp_bwd(const void*, const void*, const int*,
                       const unsigned char*, const float*, const float*,
                       const int*, const int*,
                       const unsigned char*, const float*, const float*,
-                      const float*, const float*, float*, float*, void*, int,
-                      long, int, int, int, int, float, const float*, bool,
-                      int, hipStream_t);
+                      const float*, const float*, float*, float*, float*,
+                      void*, int, long, int, int, int, int, float,
+                      const float*, bool, int, bool, hipStream_t);
 int egnmp_reduce_chunks(long, int, int);
 struct CastDesc { const float* src; void* dst; int n; };
 struct CastChunk { CastDesc d[128]; int count; };
@@ -617,12 +617,15 @@ std::vector<torch::Tensor> group_norm_act_maxpool_bwd(
 // argmax are point-major too.  GN stats over the full (M/G, K, N) edge
 // extent, identical to group_norm_act_maxpool.  channel_major_out: y is
 // written (B, M, N) instead (am/vsel stay point-major for the backward).
+// classic (here and in edge_gnmp_bwd): run the one-gather-per-iteration
+// kernels instead of the batched ones (PVRAFT_EGNMP, for A/B runs).
 std::vector<torch::Tensor> edge_gnmp_fwd(torch::Tensor wg, torch::Tensor idx,
                                          int64_t G, torch::Tensor weight,
                                          torch::Tensor bias, double eps,
                                          int64_t act, double slope,
                                          c10::optional<torch::Tensor> slope_t,
-                                         bool channel_major_out = false) {
+                                         bool channel_major_out = false,
+                                         bool classic = false) {
   const float* slope_ptr = nullptr;
   if (act == 2) {
     TORCH_CHECK(slope_t.has_value() && slope_t->numel() == 1, "act=2 needs a scalar slope tensor");
@@ -671,7 +674,8 @@ std::vector<torch::Tensor> edge_gnmp_fwd(torch::Tensor wg, torch::Tensor idx,
                    y.data_ptr(),
                    am.data_ptr<unsigned char>(), vsel.data_ptr<float>(), B, N,
                    K, M, (int)G, (float)eps, (int)act, (float)slope,
-                   slope_ptr, bf16, rchunks, channel_major_out, stream());
+                   slope_ptr, bf16, rchunks, channel_major_out, classic,
+                   stream());
   return {y, am, vsel, vsum, mean, rstd};
 }
 
@@ -684,7 +688,8 @@ std::vector<torch::Tensor> edge_gnmp_bwd(
     int64_t act, double slope, c10::optional<torch::Tensor> slope_t,
     c10::optional<torch::Tensor> wtarget = c10::nullopt,
     c10::optional<torch::Tensor> btarget = c10::nullopt,
-    c10::optional<torch::Tensor> starget = c10::nullopt) {
+    c10::optional<torch::Tensor> starget = c10::nullopt,
+    bool classic = false) {
   const float* slope_ptr = nullptr;
   if (act == 2) {
     TORCH_CHECK(slope_t.has_value() && slope_t->numel() == 1, "act=2 needs a scalar slope tensor");
@@ -708,6 +713,9 @@ std::vector<torch::Tensor> edge_gnmp_bwd(
   const int rchunks = egnmp_reduce_chunks(N, M, B);
   auto scratch = torch::empty({ws_len, (long)rchunks * B}, fopt);
   auto dwg = torch::empty_like(wg);
+  // transient: the reduce pass hands the gated dy*gamma to the apply pass
+  torch::Tensor gsel;
+  if (!classic) gsel = torch::empty({B, N, (long)M}, fopt);
   launch_egnmp_bwd(dy.data_ptr(), wg.data_ptr(), idx.data_ptr<int>(),
                    am.data_ptr<unsigned char>(), vsel.data_ptr<float>(),
                    vsum.data_ptr<float>(),
@@ -716,9 +724,10 @@ std::vector<torch::Tensor> edge_gnmp_bwd(
                    mean.data_ptr<float>(),
                    rstd.data_ptr<float>(), weight.data_ptr<float>(),
                    bias.data_ptr<float>(), scratch.data_ptr<float>(),
-                   ws.data_ptr<float>(), dwg.data_ptr(), B, N, K, M, (int)G,
-                   (int)act, (float)slope, slope_ptr, bf16, rchunks,
-                   stream());
+                   ws.data_ptr<float>(),
+                   classic ? nullptr : gsel.data_ptr<float>(), dwg.data_ptr(),
+                   B, N, K, M, (int)G, (int)act, (float)slope, slope_ptr, bf16,
+                   rchunks, classic, stream());
   return gn_grads_finish(ws, dwg, rows, M, fopt, wtarget, btarget, starget);
 }
 
@@ -1712,8 +1721,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("idx"), pybind11::arg("G"), pybind11::arg("weight"),
         pybind11::arg("bias"), pybind11::arg("eps"), pybind11::arg("act"),
         pybind11::arg("slope"), pybind11::arg("slope_t"),
-        pybind11::arg("channel_major_out") = false);
-  m.def("edge_gnmp_bwd", &edge_gnmp_bwd);
+        pybind11::arg("channel_major_out") = false,
+        pybind11::arg("classic") = false);
+  m.def("edge_gnmp_bwd", &edge_gnmp_bwd, pybind11::arg("dy"),
+        pybind11::arg("wg"), pybind11::arg("idx"), pybind11::arg("am"),
+        pybind11::arg("vsel"), pybind11::arg("vsum"),
+        pybind11::arg("offsets"), pybind11::arg("order_n"),
+        pybind11::arg("order_j"), pybind11::arg("mean"),
+        pybind11::arg("rstd"), pybind11::arg("G"), pybind11::arg("weight"),
+        pybind11::arg("bias"), pybind11::arg("act"), pybind11::arg("slope"),
+        pybind11::arg("slope_t"), pybind11::arg("wtarget"),
+        pybind11::arg("btarget"), pybind11::arg("starget"),
+        pybind11::arg("classic") = false);
   m.def("morton_keys", &morton_keys);
   m.def("multi_cast_bf16", &multi_cast_bf16);
   m.def("knn_gnmp_fwd", &knn_gnmp_fwd, pybind11::arg("raw"),

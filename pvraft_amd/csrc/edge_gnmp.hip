@@ -45,10 +45,19 @@
 // gather sum the forward reduce stores) -- no K-loop in the apply pass.
 // The INCOMING sum walks the inverse-adjacency CSR via the (order_n,
 // order_j) side arrays -- source point and neighbour slot per ordered
-// edge, no id decomposition, dy a scalar load only on the argmax hit;
-// every (p, m) output is written exactly once.
+// edge, no id decomposition; every (p, m) output is written exactly once.
+//
+// Two sets of kernels compute this.  The default ones keep several
+// gathers in flight per thread (groups of EG_U neighbours / incoming
+// edges) and pass the gated dy*gamma from the backward reduce to the
+// apply pass (gsel), so neither backward pass re-derives what another
+// pass already holds.  The one-gather-per-iteration kernels they replace
+// stay reachable (PVRAFT_EGNMP=classic, read in ops/__init__.py) for
+// paired A/B runs; thread mapping, arithmetic and summation order are the
+// same in both sets.
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
+#include <cstdint>
 #include "common.h"
 
 #define EG_THREADS 256
@@ -160,6 +169,159 @@ __global__ __launch_bounds__(EG_THREADS) void egnmp_fwd_reduce_kernel(
       *(uchar4 *)(amin + pi) = an;
       // per-point gather sum: lets the backward centre term close over j
       // (sum_j xhat_j derives from it) with no K-loop at all
+      *(float4 *)(vsum + pi) =
+          make_float4(ps[0], ps[1], ps[2], ps[3]);
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int g = (c4 * 4 + e) / Cg;
+      atomicAdd(&wbins[(b * G + g) * 2 + 0], s[e]);
+      atomicAdd(&wbins[(b * G + g) * 2 + 1], ss[e]);
+    }
+  }
+  __syncthreads();
+  const long col = (long)blockIdx.x * B + b;
+  const long stride = (long)gridDim.x * B;
+  for (unsigned i = threadIdx.x; i < (unsigned)n_out; i += EG_THREADS) {
+    float v = bins[i];
+#pragma unroll
+    for (int w = 1; w < NW; ++w) v += bins[w * n_out + i];
+    scratch[i * stride + col] = v;
+  }
+}
+
+// Default forward reduce: the same thread mapping, arithmetic and j order
+// as egnmp_fwd_reduce_kernel above (outputs are bit-identical), but the
+// K-loop runs in groups of EG_U neighbours.  The classic loop has ONE
+// dependent gather in flight per thread (row[j], then wg[row[j]]) and the
+// grid is only ~4 waves per SIMD, so it is L2-latency-bound; here a group's
+// indices arrive as 16-byte loads (when the rows are 16-byte aligned), all
+// EG_U neighbour quads are issued before the first is used, and the next
+// group's indices are fetched under them.  K % EG_U neighbours run the
+// classic way.
+#define EG_U 8
+
+template <int U>
+DEV_INLINE void eg_load_idx(const int *__restrict__ p, bool vec,
+                            int (&o)[U]) {
+  static_assert(U % 4 == 0, "group size must be a multiple of 4");
+  if (vec) {
+#pragma unroll
+    for (int q = 0; q < U / 4; ++q) {
+      const int4 t = ((const int4 *)p)[q];
+      o[q * 4 + 0] = t.x; o[q * 4 + 1] = t.y;
+      o[q * 4 + 2] = t.z; o[q * 4 + 3] = t.w;
+    }
+  } else {
+#pragma unroll
+    for (int u = 0; u < U; ++u) o[u] = p[u];
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(EG_THREADS) void egnmp_fwd_reduce_batched_kernel(
+    const T *__restrict__ wg,      // (B, N, M)
+    const int *__restrict__ idx,   // (B, N, K)
+    float *__restrict__ scratch,   // (B*G*2, gridX*B)
+    float *__restrict__ vmax, float *__restrict__ vmin,  // (B, N, M) fp32
+    unsigned char *__restrict__ amax,
+    unsigned char *__restrict__ amin,                  // (B, N, M)
+    float *__restrict__ vsum,      // (B, N, M): sum_j v per point (fp32)
+    long N, int K, int M, int G,
+    int idx_vec) {  // every idx row starts on a 16-byte boundary
+  constexpr int U = EG_U;
+  const int b = blockIdx.z;
+  const int B = gridDim.z;
+  const int tpc = M / 4;                 // threads per point (quad each)
+  const int ppb = EG_THREADS / tpc;      // points per block iteration
+  const int p_l = (int)threadIdx.x / tpc;
+  const int c4 = (int)threadIdx.x % tpc;
+  const bool active = p_l < ppb;
+  const int Cg = M / G;
+  const int n_out = B * G * 2;
+  const int Kg = K - K % U;              // neighbours handled in groups
+
+  extern __shared__ float bins[];  // (waves, B*G*2); only this block's b
+  constexpr int NW = EG_THREADS / WAVE;
+  for (unsigned i = threadIdx.x; i < (unsigned)(n_out * NW); i += EG_THREADS)
+    bins[i] = 0.f;
+  float *wbins = bins + wave_id() * n_out;
+  __syncthreads();
+
+  const T *wgb = wg + (long)b * N * M;
+  const int *idxb = idx + (long)b * N * K;
+  float s[4] = {0.f, 0.f, 0.f, 0.f}, ss[4] = {0.f, 0.f, 0.f, 0.f};
+  if (active) {
+    for (long n = (long)blockIdx.x * ppb + p_l; n < N;
+         n += (long)gridDim.x * ppb) {
+      const Quad<T> cq = *(const Quad<T> *)(wgb + n * M + c4 * 4);
+      const int *row = idxb + n * K;
+      float vmx[4], vmn[4], ps[4] = {0.f, 0.f, 0.f, 0.f};
+      int jmx[4] = {0, 0, 0, 0}, jmn[4] = {0, 0, 0, 0};
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        vmx[e] = -INFINITY;
+        vmn[e] = INFINITY;
+      }
+      int nb[U];
+      if (Kg > 0) eg_load_idx<U>(row, idx_vec, nb);
+      int j = 0;
+      for (; j < Kg; j += U) {
+        Quad<T> nq[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+          nq[u] = *(const Quad<T> *)(wgb + (long)nb[u] * M + c4 * 4);
+        if (j + U < Kg) eg_load_idx<U>(row + j + U, idx_vec, nb);
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const float v = (float)nq[u].v[e] - (float)cq.v[e];
+            ps[e] += v;
+            // the classic loop's v * v + ss compiles to one fma; spelled
+            // out here, where the unrolled group would otherwise leave
+            // some of them as a separate multiply and add
+            ss[e] = __builtin_fmaf(v, v, ss[e]);
+            if (v > vmx[e]) {
+              vmx[e] = v;
+              jmx[e] = j + u;
+            }
+            if (v < vmn[e]) {
+              vmn[e] = v;
+              jmn[e] = j + u;
+            }
+          }
+        }
+      }
+      for (; j < K; ++j) {
+        const Quad<T> nq = *(const Quad<T> *)(wgb + (long)row[j] * M + c4 * 4);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const float v = (float)nq.v[e] - (float)cq.v[e];
+          ps[e] += v;
+          ss[e] = __builtin_fmaf(v, v, ss[e]);
+          if (v > vmx[e]) {
+            vmx[e] = v;
+            jmx[e] = j;
+          }
+          if (v < vmn[e]) {
+            vmn[e] = v;
+            jmn[e] = j;
+          }
+        }
+      }
+#pragma unroll
+      for (int e = 0; e < 4; ++e) s[e] += ps[e];
+      uchar4 ax, an;
+      ax.x = (unsigned char)jmx[0]; ax.y = (unsigned char)jmx[1];
+      ax.z = (unsigned char)jmx[2]; ax.w = (unsigned char)jmx[3];
+      an.x = (unsigned char)jmn[0]; an.y = (unsigned char)jmn[1];
+      an.z = (unsigned char)jmn[2]; an.w = (unsigned char)jmn[3];
+      const long pi = ((long)b * N + n) * M + c4 * 4;
+      *(float4 *)(vmax + pi) = make_float4(vmx[0], vmx[1], vmx[2], vmx[3]);
+      *(float4 *)(vmin + pi) = make_float4(vmn[0], vmn[1], vmn[2], vmn[3]);
+      *(uchar4 *)(amax + pi) = ax;
+      *(uchar4 *)(amin + pi) = an;
       *(float4 *)(vsum + pi) =
           make_float4(ps[0], ps[1], ps[2], ps[3]);
     }
@@ -582,6 +744,230 @@ __global__ __launch_bounds__(EG_THREADS) void egnmp_bwd_apply_kernel(
   }
 }
 
+// Default backward, pass 1: the same sums, thread mapping, per-wave bins
+// and fold order as egnmp_bwd_reduce_kernel, as a STREAMING pass.  The
+// pre-GN value at the argmax is the float the forward saved as vsel (the
+// classic kernel re-derives it with a divergent idx load and four scalar
+// wg gathers per thread), so idx, wg and am are not read.  The gated
+// dy*gamma it forms per (n, c) is also what the apply pass needs for the
+// centre term and for every argmax hit of an incoming edge; it is stored
+// once, fp32 point-major, in the transient gsel.
+template <typename T, int ACT>
+__global__ __launch_bounds__(EG_THREADS) void egnmp_bwd_reduce_stream_kernel(
+    const T *__restrict__ dy,          // (B, N, M) pooled grad (point-major)
+    const float *__restrict__ vsel,    // (B, N, M): pre-GN value at argmax
+    const float *__restrict__ mean, const float *__restrict__ rstd,
+    const float *__restrict__ gamma, const float *__restrict__ beta,
+    float *__restrict__ scratch,
+    float *__restrict__ gsel,          // (B, N, M) out: gated dy * gamma
+    long N, int M, int G, float slope, const float *__restrict__ slope_ptr) {
+  const int b = blockIdx.z;
+  const int B = gridDim.z;
+  const int tpc = M / 4;
+  const int ppb = EG_THREADS / tpc;
+  const int p_l = (int)threadIdx.x / tpc;
+  const int c4 = (int)threadIdx.x % tpc;
+  const bool active = p_l < ppb;
+  const int Cg = M / G;
+  if (ACT == 2) slope = *slope_ptr;
+
+  extern __shared__ float sbins_all[];
+  constexpr int NW = EG_THREADS / WAVE;
+  const int n_out = G * 2 * B + M * 2 + 1;
+  for (unsigned i = threadIdx.x; i < (unsigned)(n_out * NW); i += EG_THREADS)
+    sbins_all[i] = 0.f;
+  float *sbins = sbins_all + wave_id() * n_out;
+  __syncthreads();
+
+  float sum_dx[4] = {}, sum_dxx[4] = {}, c_dg[4] = {}, c_db[4] = {};
+  float d_sl = 0.f;
+  float m[4], r[4], ga[4], be[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const int c = c4 * 4 + e;
+    m[e] = mean[b * G + c / Cg];
+    r[e] = rstd[b * G + c / Cg];
+    ga[e] = gamma[c];
+    be[e] = beta[c];
+  }
+  if (active) {
+    for (long n = (long)blockIdx.x * ppb + p_l; n < N;
+         n += (long)gridDim.x * ppb) {
+      const long pi = ((long)b * N + n) * M + c4 * 4;
+      const Quad<T> gq = *(const Quad<T> *)(dy + pi);
+      const float4 sv = *(const float4 *)(vsel + pi);
+      const float vs[4] = {sv.x, sv.y, sv.z, sv.w};
+      float dxs[4];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float xhat = (vs[e] - m[e]) * r[e];
+        float gv = (float)gq.v[e];
+        if (ACT >= 1) {
+          const float pre = xhat * ga[e] + be[e];
+          if (ACT == 2 && pre <= 0.f) d_sl += gv * pre;
+          gv = pre > 0.f ? gv : gv * slope;
+        }
+        c_db[e] += gv;
+        c_dg[e] += gv * xhat;
+        const float dxhat = gv * ga[e];
+        sum_dx[e] += dxhat;
+        sum_dxx[e] += dxhat * xhat;
+        dxs[e] = dxhat;
+      }
+      *(float4 *)(gsel + pi) = make_float4(dxs[0], dxs[1], dxs[2], dxs[3]);
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int c = c4 * 4 + e;
+      const int g = c / Cg;
+      atomicAdd(&sbins[(b * G + g) * 2 + 0], sum_dx[e]);
+      atomicAdd(&sbins[(b * G + g) * 2 + 1], sum_dxx[e]);
+      atomicAdd(&sbins[G * 2 * B + c * 2 + 0], c_db[e]);
+      atomicAdd(&sbins[G * 2 * B + c * 2 + 1], c_dg[e]);
+    }
+    if (ACT == 2) atomicAdd(&sbins[G * 2 * B + M * 2], d_sl);
+  }
+  __syncthreads();
+  const long col = (long)blockIdx.x * B + b;
+  const long stride = (long)gridDim.x * B;
+  for (unsigned i = threadIdx.x; i < (unsigned)n_out; i += EG_THREADS) {
+    float v = sbins_all[i];
+#pragma unroll
+    for (int w = 1; w < NW; ++w) v += sbins_all[w * n_out + i];
+    scratch[i * stride + col] = v;
+  }
+}
+
+// Default backward, pass 2: the same terms summed in the same order as
+// egnmp_bwd_apply_kernel (centre first, then the incoming edges in CSR
+// order), without dy and without a branch per channel.  The centre term
+// and every argmax hit take the gated dy*gamma from gsel.  The incoming
+// walk goes in groups of EG_U edges: the group's wg and am quads are all
+// issued before the first use, the next group's (ordn, ordj) are fetched
+// under them, and a lane loads a source point's gsel quad (one 16-byte
+// load) only where one of its four channels has that edge's slot as its
+// argmax.  Slots past the end of the list read the list's last edge and
+// are dropped by a select, so every list length takes the same path and
+// no address leaves [lo, hi).
+template <typename T>
+__global__ __launch_bounds__(EG_THREADS) void egnmp_bwd_apply_batched_kernel(
+    const T *__restrict__ wg, const unsigned char *__restrict__ am,
+    const float *__restrict__ gsel,   // (B, N, M): gated dy * gamma
+    const float *__restrict__ vsum,   // (B, N, M): sum_j v per point
+    const int *__restrict__ offsets,  // (B, N+1)
+    const int *__restrict__ ordn,     // (B, K*N): source n per ordered edge
+    const unsigned char *__restrict__ ordj,  // (B, K*N): its neighbour slot
+    const float *__restrict__ mean, const float *__restrict__ rstd,
+    const float *__restrict__ row_ws, T *__restrict__ dwg, long N, int K,
+    int M, int G, long row_len) {
+  constexpr int U = EG_U;
+  const int b = blockIdx.z;
+  const int tpc = M / 4;
+  const int ppb = EG_THREADS / tpc;
+  const int p_l = (int)threadIdx.x / tpc;
+  const int c4 = (int)threadIdx.x % tpc;
+  if (p_l >= ppb) return;
+  const int Cg = M / G;
+  const float inv_n = 1.0f / (float)row_len;
+  float m[4], r[4], s1[4], s2[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const int row = b * G + (c4 * 4 + e) / Cg;
+    m[e] = mean[row];
+    r[e] = rstd[row];
+    s1[e] = row_ws[row * 2 + 0];
+    s2[e] = row_ws[row * 2 + 1];
+  }
+
+  const T *wgb = wg + (long)b * N * M + c4 * 4;
+  const unsigned char *amb = am + (long)b * N * M + c4 * 4;
+  const float *gselb = gsel + (long)b * N * M + c4 * 4;
+  const float *vsumb = vsum + (long)b * N * M + c4 * 4;
+  const int *ordnb = ordn + (long)b * N * K;
+  const unsigned char *ordjb = ordj + (long)b * N * K;
+  const int *offb = offsets + (long)b * (N + 1);
+
+  for (long p = (long)blockIdx.x * ppb + p_l; p < N;
+       p += (long)gridDim.x * ppb) {
+    const Quad<T> pq = *(const Quad<T> *)(wgb + p * M);
+    float acc[4];
+    // centre term, closed over j (see egnmp_bwd_apply_kernel)
+    {
+      const float4 gc = *(const float4 *)(gselb + p * M);
+      const float4 vs = *(const float4 *)(vsumb + p * M);
+      const float gcs[4] = {gc.x, gc.y, gc.z, gc.w};
+      const float vss[4] = {vs.x, vs.y, vs.z, vs.w};
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float sum_xhat = (vss[e] - (float)K * m[e]) * r[e];
+        acc[e] = -gcs[e] * r[e] +
+                 ((float)K * s1[e] + sum_xhat * s2[e]) * inv_n * r[e];
+      }
+    }
+    const int lo = offb[p], hi = offb[p + 1];
+    if (lo < hi) {
+      int nn[U], jj[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int tt = min(lo + u, hi - 1);
+        nn[u] = ordnb[tt];
+        jj[u] = ordjb[tt];
+      }
+      for (int t = lo; t < hi; t += U) {
+        Quad<T> nq[U];
+        uchar4 aq[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          nq[u] = *(const Quad<T> *)(wgb + (long)nn[u] * M);
+          aq[u] = *(const uchar4 *)(amb + (long)nn[u] * M);
+        }
+        int nn2[U], jj2[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          const int tt = min(t + U + u, hi - 1);
+          nn2[u] = ordnb[tt];
+          jj2[u] = ordjb[tt];
+        }
+        float4 gq[U];
+        unsigned hit[U];  // bit e: channel e's argmax is this edge's slot
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          const unsigned h = (unsigned)(jj[u] == (int)aq[u].x) |
+                             ((unsigned)(jj[u] == (int)aq[u].y) << 1) |
+                             ((unsigned)(jj[u] == (int)aq[u].z) << 2) |
+                             ((unsigned)(jj[u] == (int)aq[u].w) << 3);
+          hit[u] = (t + u < hi) ? h : 0u;
+          gq[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+          if (hit[u]) gq[u] = *(const float4 *)(gselb + (long)nn[u] * M);
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          const bool valid = t + u < hi;
+          const float gs[4] = {gq[u].x, gq[u].y, gq[u].z, gq[u].w};
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const float v = (float)pq.v[e] - (float)nq[u].v[e];
+            const float xhat = (v - m[e]) * r[e];
+            const float dxhat = (hit[u] >> e) & 1u ? gs[e] : 0.f;
+            const float term =
+                (dxhat - (s1[e] + xhat * s2[e]) * inv_n) * r[e];
+            acc[e] = valid ? acc[e] + term : acc[e];
+          }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          nn[u] = nn2[u];
+          jj[u] = jj2[u];
+        }
+      }
+    }
+    Quad<T> oq;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) oq.v[e] = (T)acc[e];
+    *(Quad<T> *)(dwg + ((long)b * N + p) * M + c4 * 4) = oq;
+  }
+}
+
 // --------------------------------------------------------------- launchers
 
 static int eg_chunks(long N, int ppb, int B, int cap) {
@@ -601,13 +987,21 @@ void egnmp_fwd_impl(const T *wg, const int *idx, float *scratch, float *ws,
                     unsigned char *am, float *vsel,
                     int B, long N, int K, int M, int G, float eps, int act,
                     float slope, const float *slope_ptr, int rchunks,
-                    bool channel_major, hipStream_t stream) {
+                    bool channel_major, bool classic, hipStream_t stream) {
   const dim3 rgrid(rchunks, 1, B);
   const int n_out_f = B * G * 2;
-  hipLaunchKernelGGL(egnmp_fwd_reduce_kernel<T>, rgrid, dim3(EG_THREADS),
-                     (size_t)n_out_f * (EG_THREADS / WAVE) * sizeof(float),
-                     stream, wg, idx,
-                     scratch, vmax, vmin, amax, amin, vsum, N, K, M, G);
+  const size_t shmem_f =
+      (size_t)n_out_f * (EG_THREADS / WAVE) * sizeof(float);
+  if (classic) {
+    hipLaunchKernelGGL(egnmp_fwd_reduce_kernel<T>, rgrid, dim3(EG_THREADS),
+                       shmem_f, stream, wg, idx, scratch, vmax, vmin, amax,
+                       amin, vsum, N, K, M, G);
+  } else {
+    const int idx_vec = K % 4 == 0 && (uintptr_t)idx % 16 == 0;
+    hipLaunchKernelGGL(egnmp_fwd_reduce_batched_kernel<T>, rgrid,
+                       dim3(EG_THREADS), shmem_f, stream, wg, idx, scratch,
+                       vmax, vmin, amax, amin, vsum, N, K, M, G, idx_vec);
+  }
   (void)ws;
   launch_gn_finalize_scratch(scratch, (long)rchunks * B, mean, rstd,
                              (long)(M / G) * K * N, B * G, eps, stream);
@@ -623,9 +1017,9 @@ void egnmp_bwd_impl(const T *dy, const T *wg, const int *idx,
                     const int *ordn, const unsigned char *ordj,
                     const float *mean,
                     const float *rstd, const float *gamma, const float *beta,
-                    float *scratch, float *ws, T *dwg, int B, long N, int K,
-                    int M, int G, int act, float slope,
-                    const float *slope_ptr, int rchunks,
+                    float *scratch, float *ws, float *gsel, T *dwg, int B,
+                    long N, int K, int M, int G, int act, float slope,
+                    const float *slope_ptr, int rchunks, bool classic,
                     hipStream_t stream) {
   const int tpc = M / 4;
   const int ppb = EG_THREADS / tpc;
@@ -650,10 +1044,31 @@ void egnmp_bwd_impl(const T *dy, const T *wg, const int *idx,
                        offsets, ordn, ordj, mean, rstd, gamma, beta, ws, dwg,  \
                        N, K, M, G, row_len, slope, slope_ptr);                 \
   } while (0)
-  if (act == 2) EG_BWD(2);
-  else if (act == 1) EG_BWD(1);
-  else EG_BWD(0);
+#define EG_BWD_STREAM(A)                                                       \
+  do {                                                                         \
+    hipLaunchKernelGGL((egnmp_bwd_reduce_stream_kernel<T, A>), rgrid,          \
+                       dim3(EG_THREADS), shmem, stream, dy, vsel, mean, rstd,  \
+                       gamma, beta, scratch, gsel, N, M, G, slope, slope_ptr); \
+    hipLaunchKernelGGL(egnmp_sum_partials_kernel,                              \
+                       dim3((n_out + waves_per_block - 1) / waves_per_block),  \
+                       dim3(EG_THREADS), 0, stream, scratch, ws,               \
+                       (long)rchunks * B, n_out);                              \
+    hipLaunchKernelGGL(egnmp_bwd_apply_batched_kernel<T>, agrid,               \
+                       dim3(EG_THREADS), 0, stream, wg, am, gsel, vsum,        \
+                       offsets, ordn, ordj, mean, rstd, ws, dwg, N, K, M, G,   \
+                       row_len);                                               \
+  } while (0)
+  if (classic) {
+    if (act == 2) EG_BWD(2);
+    else if (act == 1) EG_BWD(1);
+    else EG_BWD(0);
+  } else {
+    if (act == 2) EG_BWD_STREAM(2);
+    else if (act == 1) EG_BWD_STREAM(1);
+    else EG_BWD_STREAM(0);
+  }
 #undef EG_BWD
+#undef EG_BWD_STREAM
 }
 
 // Standalone pick launcher for sibling fused ops (csrc/knn_gnmp.hip):
@@ -693,7 +1108,7 @@ void launch_egnmp_fwd(const void *wg, const int *idx, float *scratch,
                       void *y, unsigned char *am, float *vsel, int B, long N,
                       int K, int M, int G, float eps, int act, float slope,
                       const float *slope_ptr, bool bf16, int rchunks,
-                      bool channel_major, hipStream_t stream) {
+                      bool channel_major, bool classic, hipStream_t stream) {
   if (bf16)
     egnmp_fwd_impl<__hip_bfloat16>((const __hip_bfloat16 *)wg, idx, scratch,
                                    ws, mean, rstd, gamma, beta,
@@ -701,13 +1116,13 @@ void launch_egnmp_fwd(const void *wg, const int *idx, float *scratch,
                                    (__hip_bfloat16 *)y, am,
                                    vsel, B, N, K,
                                    M, G, eps, act, slope, slope_ptr, rchunks,
-                                   channel_major, stream);
+                                   channel_major, classic, stream);
   else
     egnmp_fwd_impl<float>((const float *)wg, idx, scratch, ws, mean, rstd,
                           gamma, beta, vmax, vmin, amax,
                           amin, vsum, (float *)y, am, vsel, B, N, K,
                           M, G, eps, act, slope, slope_ptr, rchunks,
-                          channel_major, stream);
+                          channel_major, classic, stream);
 }
 
 void launch_egnmp_bwd(const void *dy, const void *wg, const int *idx,
@@ -717,20 +1132,21 @@ void launch_egnmp_bwd(const void *dy, const void *wg, const int *idx,
                       const float *mean,
                       const float *rstd, const float *gamma,
                       const float *beta, float *scratch, float *ws,
-                      void *dwg, int B, long N, int K, int M, int G, int act,
-                      float slope, const float *slope_ptr, bool bf16,
-                      int rchunks, hipStream_t stream) {
+                      float *gsel, void *dwg, int B, long N, int K, int M,
+                      int G, int act, float slope, const float *slope_ptr,
+                      bool bf16, int rchunks, bool classic,
+                      hipStream_t stream) {
   if (bf16)
     egnmp_bwd_impl<__hip_bfloat16>(
         (const __hip_bfloat16 *)dy, (const __hip_bfloat16 *)wg, idx, am,
         vsel, vsum,
-        offsets, ordn, ordj, mean, rstd, gamma, beta, scratch, ws,
+        offsets, ordn, ordj, mean, rstd, gamma, beta, scratch, ws, gsel,
         (__hip_bfloat16 *)dwg, B, N, K, M, G, act, slope, slope_ptr, rchunks,
-        stream);
+        classic, stream);
   else
     egnmp_bwd_impl<float>((const float *)dy, (const float *)wg, idx, am,
                           vsel, vsum,
                           offsets, ordn, ordj, mean, rstd, gamma, beta,
-                          scratch, ws, (float *)dwg, B, N, K, M, G, act,
-                          slope, slope_ptr, rchunks, stream);
+                          scratch, ws, gsel, (float *)dwg, B, N, K, M, G, act,
+                          slope, slope_ptr, rchunks, classic, stream);
 }

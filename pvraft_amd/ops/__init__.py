@@ -97,6 +97,14 @@ def channel_major_layout() -> bool:
     return os.environ.get("PVRAFT_SETCONV_LAYOUT", "fused") != "classic"
 
 
+def egnmp_classic() -> tuple:
+    """(forward, backward) use the one-gather-per-iteration edge_gnmp
+    kernels instead of the batched ones: PVRAFT_EGNMP=classic switches
+    both, classic_fwd / classic_bwd one side only (paired A/B runs)."""
+    mode = os.environ.get("PVRAFT_EGNMP", "batched")
+    return (mode in ("classic", "classic_fwd"), mode in ("classic", "classic_bwd"))
+
+
 # ---------------------------------------------------------------------------
 # autograd wrappers around the HIP kernels
 # ---------------------------------------------------------------------------
@@ -341,7 +349,8 @@ class _EdgeGNMP(torch.autograd.Function):
         b = bias.float().contiguous()
         st_ = slope_t.float().reshape(1).contiguous() if slope_t is not None else None
         y, am, vsel, vsum, mean, rstd = _EXT.edge_gnmp_fwd(
-            wg_t, idx, num_groups, w, b, eps, act, slope, st_, channel_major_out)
+            wg_t, idx, num_groups, w, b, eps, act, slope, st_, channel_major_out,
+            egnmp_classic()[0])
         ctx.save_for_backward(wg_t, idx, am, vsel, vsum, offsets, order_n, order_j, mean, rstd, w, b, st_)
         ctx.conf = (num_groups, act, slope, weight.dtype)
         ctx.channel_major_out = channel_major_out
@@ -359,12 +368,13 @@ class _EdgeGNMP(torch.autograd.Function):
             # the autograd of the caller's output transpose did before
             dy = _EXT.batched_transpose(dy)
         tgt = _gn_defer_targets(*ctx.params, act)
+        classic = egnmp_classic()[1]
         if tgt is not None:
             (dwg,) = _EXT.edge_gnmp_bwd(
                 dy.contiguous(), wg_t, idx, am, vsel, vsum, offsets,
                 order_n, order_j,
                 mean, rstd, num_groups, w, b, act, slope, st_,
-                tgt[0], tgt[1], tgt[2],
+                tgt[0], tgt[1], tgt[2], classic,
             )
             return (dwg, None, None, None, None, None, None, None, None,
                     None, None, None, None)
@@ -372,6 +382,7 @@ class _EdgeGNMP(torch.autograd.Function):
             dy.contiguous(), wg_t, idx, am, vsel, vsum, offsets, order_n,
             order_j,
             mean, rstd, num_groups, w, b, act, slope, st_, None, None, None,
+            classic,
         )
         dslope = dsl.to(wdtype) if act == 2 else None
         return (dwg, None, None, None, None, None, dw.to(wdtype),
