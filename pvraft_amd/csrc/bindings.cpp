@@ -51,6 +51,13 @@ void launch_cluster_points(const float*, const float*, const unsigned char*,
                            int*, int*, int*, int*, int*, int, int, int, float,
                            float, int, hipStream_t);
 int cluster_tile();
+void launch_voxel_sample(const float*, const unsigned char*, unsigned long long*,
+                         unsigned long long*, int*, unsigned char*, int*, int*,
+                         long*, int*, int*, int*, int, int, int, long, int,
+                         float, unsigned, hipStream_t);
+int voxel_sample_block();
+int voxel_sample_scan();
+long voxel_sample_meta();
 void launch_morton_keys(const float*, const float*, const float*, long*,
                         int, long, hipStream_t);
 void launch_gather_edge_fwd(const void*, const int*, const float*, void*,
@@ -1680,7 +1687,65 @@ std::vector<torch::Tensor> plane_fit(torch::Tensor xyz,
   return {normal, offset, height, ground, inlier, count, best, rounds, ok};
 }
 
+// Voxel-stratified sampling (csrc/voxel_sample.hip).  xyz (B,N,3) f32,
+// optional mask (B,N) bool, inv = fp32(1 / voxel) from the caller so every
+// backend multiplies by the same number -> {idx (B,m) i64, count (B) i32,
+// rank (B,N) i32, occupied (B,levels) i32}.  10 + levels launches, no host
+// synchronisation.  The workspaces are torch allocations of this call; the
+// first kernel initialises every word that is read before it is written.
+std::vector<torch::Tensor> voxel_sample(torch::Tensor xyz,
+                                        c10::optional<torch::Tensor> mask,
+                                        int64_t m, double inv, int64_t levels,
+                                        int64_t seed) {
+  check_f32(xyz, "xyz");
+  TORCH_CHECK(xyz.dim() == 3 && xyz.size(2) == 3, "xyz must be (B,N,3)");
+  const int64_t B = xyz.size(0), N = xyz.size(1);
+  TORCH_CHECK(B >= 1 && B <= 65535 && N >= 1, "voxel_sample requires 1 <= B <= 65535, N >= 1");
+  TORCH_CHECK(N < (1L << 27), "voxel_sample requires N < 2^27");
+  TORCH_CHECK(m >= 1, "voxel_sample requires m >= 1");
+  TORCH_CHECK(levels >= 1 && levels <= 16, "voxel_sample requires 1 <= levels <= 16");
+  TORCH_CHECK(inv > 0.0 && std::isfinite(inv), "voxel_sample requires a finite 1 / voxel > 0");
+  const unsigned char* mp = nullptr;
+  if (mask.has_value()) {
+    const torch::Tensor& k = *mask;
+    TORCH_CHECK(k.is_cuda() && k.is_contiguous() &&
+                    k.scalar_type() == torch::kBool && k.dim() == 2 &&
+                    k.size(0) == B && k.size(1) == N &&
+                    k.device() == xyz.device(),
+                "mask must be contiguous bool (B,N) on the device of xyz");
+    mp = reinterpret_cast<const unsigned char*>(k.data_ptr<bool>());
+  }
+  int64_t T = 2;  // slots per table and cloud: a power of two >= 2 N
+  while (T < 2 * N) T <<= 1;
+  const int64_t nblk = (N + voxel_sample_block() - 1) / voxel_sample_block();
+  auto iopt = xyz.options().dtype(torch::kInt32);
+  auto lopt = xyz.options().dtype(torch::kInt64);
+  auto tab = torch::empty({6, B, T}, lopt);
+  auto key0 = torch::empty({B, N}, lopt);
+  auto slots = torch::empty({2, B, N}, iopt);
+  auto sel = torch::empty({B, N}, xyz.options().dtype(torch::kUInt8));
+  auto bsum = torch::empty({B, nblk}, iopt);
+  auto meta = torch::empty({B, (int64_t)voxel_sample_meta()}, iopt);
+  auto idx = torch::empty({B, m}, lopt);
+  auto count = torch::empty({B}, iopt);
+  auto rank = torch::empty({B, N}, iopt);
+  auto occ = torch::empty({B, levels}, iopt);
+  launch_voxel_sample(
+      xyz.data_ptr<float>(), mp,
+      reinterpret_cast<unsigned long long*>(tab.data_ptr<int64_t>()),
+      reinterpret_cast<unsigned long long*>(key0.data_ptr<int64_t>()),
+      slots.data_ptr<int>(), sel.data_ptr<uint8_t>(), bsum.data_ptr<int>(),
+      meta.data_ptr<int>(), reinterpret_cast<long*>(idx.data_ptr<int64_t>()),
+      count.data_ptr<int>(), rank.data_ptr<int>(), occ.data_ptr<int>(), (int)B,
+      (int)N, (int)T, (long)m, (int)levels, (float)inv,
+      (unsigned)(seed & 0xffffffffL), stream());
+  return {idx, count, rank, occ};
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  m.def("voxel_sample", &voxel_sample);
+  m.attr("VOXEL_SAMPLE_BLOCK") = voxel_sample_block();
+  m.attr("VOXEL_SAMPLE_SCAN") = voxel_sample_scan();
   m.def("plane_fit", &plane_fit);
   m.attr("PLANE_SCORE_TILE") = plane_score_tile();
   m.attr("PLANE_SCORE_BLOCK") = plane_score_block();

@@ -20,6 +20,11 @@ class SceneFlowDataset(Dataset):
     # flow_full (1,n,3)], the first cloud and its ground truth BEFORE
     # subsampling (dense-flow evaluation)
     return_full = False
+    # opt-in: items also carry "full2": [pc2_full (1,m,3)], the second cloud
+    # BEFORE subsampling, under the same contract (a reference to the
+    # pre-subsample array, no extra RNG draw): evaluation that draws its own
+    # samples from both full clouds (ops.voxel_sample)
+    return_full2 = False
     # opt-in: loaders that strip the ground with a fixed rule (Kitti: y < -1.4)
     # keep it, for users who segment the ground themselves (ops.fit_plane)
     keep_ground = False
@@ -46,11 +51,14 @@ class SceneFlowDataset(Dataset):
             # references to the pre-subsample arrays (subsample_points
             # rebinds, never mutates); no extra RNG draw
             full = [sequence[0], ground_truth[0], ground_truth[1]]
+        full2 = [sequence[1]] if self.return_full2 else None
         sequence, ground_truth = self.subsample_points(sequence, ground_truth)
         sequence, ground_truth = self.to_torch(sequence, ground_truth)
         data = {"sequence": sequence, "ground_truth": ground_truth}
         if full is not None:
             data["full"] = self.to_torch(full, [])[0]
+        if full2 is not None:
+            data["full2"] = self.to_torch(full2, [])[0]
         return data
 
     @staticmethod

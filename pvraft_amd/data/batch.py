@@ -29,6 +29,12 @@ class Batch:
                     f'"full" clouds are ragged and cannot be batched: got {len(samples)} samples, need 1'
                 )
             self.data["full"] = list(samples[0]["full"])
+        if any("full2" in s for s in samples):
+            if len(samples) != 1:
+                raise ValueError(
+                    f'"full2" clouds are ragged and cannot be batched: got {len(samples)} samples, need 1'
+                )
+            self.data["full2"] = list(samples[0]["full2"])
 
     def __getitem__(self, key: str):
         return self.data[key]

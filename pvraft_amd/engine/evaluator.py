@@ -43,6 +43,18 @@ masked out through ground_truth[0].  --keep_ground makes the KITTI loader
 keep its y < -1.4 points; ground_iou then compares the fitted ground with
 that rule on pc1.  SYNTH puts 30 % of its points on a ground plane when the
 flag is on.  The sparse path and its metrics are untouched.
+
+--sample voxel (beyond the reference too) replaces the loader's uniform
+subsample: both full-resolution clouds travel with the item ("full", "full2"),
+max_points indices are drawn from each with ops.voxel_sample on the device
+(--sample_voxel, --sample_levels, --sample_seed), mask and ground-truth flow
+are taken at pc1's indices, and the usual forward and metrics follow, with
+--dense, --ego_motion, --object_motion and --ground_fit on top as before.  It
+also reports sample_cut_level, the mean over the samples of l* (the finest
+grid level with at most max_points occupied cells in pc1, every cell of which
+holds a sample; ``levels`` when there is none), and sample_cut_radius, the mean
+of sqrt(3) * voxel * 2**l*.  SYNTH builds its clouds with 4 * max_points
+points, as under --dense.  Without the flag nothing changes.
 """
 
 from __future__ import annotations
@@ -76,7 +88,8 @@ def build_eval_dataset(args):
             ds.keep_ground = True
         return ds
     if args.dataset == "SYNTH":
-        full = 4 * args.max_points if getattr(args, "dense", False) else None
+        voxel = getattr(args, "sample", "random") == "voxel"
+        full = 4 * args.max_points if getattr(args, "dense", False) or voxel else None
         return SyntheticSceneFlow(args.max_points, length=getattr(args, "synth_len", 32), seed=7,
                                   full_points=full,
                                   ground_fraction=0.3 if getattr(args, "ground_fit", False) else 0.0)
@@ -110,10 +123,21 @@ def evaluate(args):
         refine_iters=int(getattr(args, "ground_iters", 3)),
     )
     ground_iou = ground and args.dataset == "KITTI" and bool(getattr(args, "keep_ground", False))
-    if dense or ego or obj or ground:
+    sample = str(getattr(args, "sample", "random"))
+    if sample not in ("random", "voxel"):
+        raise ValueError(f'--sample must be "random" or "voxel", got {sample!r}')
+    voxel = sample == "voxel"
+    sample_kw = dict(
+        voxel=float(getattr(args, "sample_voxel", 0.1)),
+        levels=int(getattr(args, "sample_levels", 10)),
+        seed=int(getattr(args, "sample_seed", 0)),
+    )
+    if dense or ego or obj or ground or voxel:
         from pvraft_amd import ops
-    if dense:
+    if dense or voxel:
         dataset.return_full = True
+    if voxel:
+        dataset.return_full2 = True
     loader = DataLoader(
         dataset,
         batch_size=1,
@@ -145,10 +169,33 @@ def evaluate(args):
     ego_sums = [0.0] * 7
     obj_sums = [0.0] * 6
     ground_sums = [0.0] * 9
+    sample_sums = [0.0] * 2
     n_ng = 0
     n = 0
     for batch in loader:
         batch = batch.to(device, non_blocking=True)
+        if voxel:
+            # the loader's own subsample is replaced: same shapes, other points.
+            # The loader still draws it (one permutation and gather per item,
+            # wasted here): skipping it would change the numpy draws that a
+            # run without the flag makes, and the datasets stay untouched
+            pc1_all, mask_all, flow_all = batch["full"]
+            pc2_all = batch["full2"][0]
+            vs1 = ops.voxel_sample(pc1_all, args.max_points, **sample_kw)
+            vs2 = ops.voxel_sample(pc2_all, args.max_points, **sample_kw)
+            for name, vs in (("pc1", vs1), ("pc2", vs2)):
+                if int(vs.count[0]) < args.max_points:
+                    raise ValueError(
+                        f"sample {n}: {name} has {int(vs.count[0])} points the voxel sampler can use, "
+                        f"fewer than max_points = {args.max_points}"
+                    )
+            sample_idx1, sample_idx2 = vs1.idx[0], vs2.idx[0]
+            batch.data["sequence"] = [pc1_all[:, sample_idx1], pc2_all[:, sample_idx2]]
+            batch.data["ground_truth"] = [mask_all[:, sample_idx1], flow_all[:, sample_idx1]]
+            covered = (vs1.occupied[0] <= args.max_points).nonzero()
+            cut = int(covered[0]) if covered.numel() else sample_kw["levels"]
+            sample_sums[0] += cut
+            sample_sums[1] += 3.0 ** 0.5 * sample_kw["voxel"] * 2.0 ** cut
         if predictor is not None and batch["sequence"][0].shape[1] == args.max_points:
             final = predictor(batch["sequence"][0], batch["sequence"][1])
             flows = predictor.last_flows
@@ -230,6 +277,8 @@ def evaluate(args):
             np.save(os.path.join(d, "pc1.npy"), batch["sequence"][0].cpu().numpy())
             np.save(os.path.join(d, "pc2.npy"), batch["sequence"][1].cpu().numpy())
             np.save(os.path.join(d, "flow.npy"), final.cpu().numpy())
+            if voxel:
+                np.save(os.path.join(d, "sample_idx1.npy"), sample_idx1.cpu().numpy())
             if dense:
                 np.save(os.path.join(d, "pc1_full.npy"), pc1_full.cpu().numpy())
                 np.save(os.path.join(d, "flow_dense.npy"), flow_dense.cpu().numpy())
@@ -326,4 +375,11 @@ def evaluate(args):
         )
         if ground_iou:
             results["ground_iou"] = gmeans[4]
+    if voxel:
+        smeans = [v / max(n, 1) for v in sample_sums]
+        log.info(
+            f"[test {args.dataset} sample voxel={sample_kw['voxel']} levels={sample_kw['levels']} "
+            f"seed={sample_kw['seed']}] cut_level={smeans[0]:.3f} cut_radius={smeans[1]:.4f}"
+        )
+        results.update(sample_cut_level=smeans[0], sample_cut_radius=smeans[1])
     return results

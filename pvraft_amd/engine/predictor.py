@@ -122,7 +122,8 @@ class Predictor:
     def predict_dense(self, pc1_full: torch.Tensor, pc2_full: torch.Tensor, k: int = 3,
                       generator: Optional[torch.Generator] = None,
                       return_sparse: bool = False, remove_ground: bool = False,
-                      ground_kw: Optional[dict] = None):
+                      ground_kw: Optional[dict] = None, sampling: str = "random",
+                      sample_kw: Optional[dict] = None):
         """Flow for EVERY point of ``pc1_full`` ((n1,3) or (1,n1,3)).
 
         Draws ``points`` indices without replacement from each full cloud
@@ -148,9 +149,21 @@ class Predictor:
         Fewer than ``points`` non-ground points in a cloud raise ValueError.
         Compacting the non-ground indices reads their count on the host:
         one synchronisation per cloud, in this eager pre-phase only.
+
+        ``sampling="voxel"`` replaces the uniform draw of each cloud by
+        ``ops.voxel_sample(cloud, points, **sample_kw)``: spatially even,
+        deterministic (``seed`` comes from ``sample_kw``; ``generator`` is
+        not consumed) and ascending, so ``idx1`` is sorted.  With
+        ``remove_ground`` the non-ground mask goes in as the sampler's
+        ``mask`` (no compaction).  Reading the sampler's ``count`` to raise
+        the ValueError for a cloud with fewer than ``points`` usable points
+        is the one host synchronisation per cloud.  Any other ``sampling``
+        than "random" or "voxel" raises ValueError.
         """
         from pvraft_amd import ops
 
+        if sampling not in ("random", "voxel"):
+            raise ValueError(f'sampling must be "random" or "voxel", got {sampling!r}')
         batch, points = self._in1.shape[0], self._in1.shape[1]
         if batch != 1:
             raise ValueError(f"predict_dense needs a batch-1 Predictor, this one has batch={batch}")
@@ -173,6 +186,17 @@ class Predictor:
                 fit = ops.fit_plane(pc.float().unsqueeze(0), **(ground_kw or {}))
                 if ground1 is None:
                     ground1 = fit.ground[0]
+            if sampling == "voxel":
+                vs = ops.voxel_sample(pc.float().unsqueeze(0), points,
+                                      mask=~fit.ground if remove_ground else None, **(sample_kw or {}))
+                usable = int(vs.count[0])  # host sync: the count
+                if usable < points:
+                    raise ValueError(
+                        f"{name} has {usable} points the voxel sampler can use, fewer than the {points} "
+                        "the predictor samples"
+                    )
+                idx = vs.idx[0]
+            elif remove_ground:
                 keep = (~fit.ground[0]).nonzero().squeeze(1)  # host sync: the count
                 if keep.numel() < points:
                     raise ValueError(

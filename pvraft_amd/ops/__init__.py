@@ -1370,3 +1370,89 @@ def fit_plane(
     if _use_hip(xyz) and B > 0 and N > 0:
         return PlaneFit(*_EXT.plane_fit(xyz, mask, thresh, thresh2, cos2, up32[0], up32[1], up32[2], H, iters, seed))
     return PlaneFit(*reference.fit_plane(xyz, mask, thresh, thresh2, cos2, up32, H, iters, seed))
+
+
+# ---------------------------------------------------------------------------
+# voxel-stratified sampling (csrc/voxel_sample.hip)
+# ---------------------------------------------------------------------------
+
+
+class VoxelSample(NamedTuple):
+    """Result of ``voxel_sample``: idx (B,m) int64 chosen point indices,
+    ascending, padded with -1; count (B,) int32 ``min(m, eligible points)``,
+    -1 if a kernel cap was hit; rank (B,N) int32, -1 for an ineligible point,
+    else the number of grid levels (0..levels) at which the point represents
+    its cell; occupied (B,levels) int32 occupied cells per grid level."""
+
+    idx: Tensor
+    count: Tensor
+    rank: Tensor
+    occupied: Tensor
+
+
+def voxel_sample(
+    xyz: Tensor, m: int, voxel: float = 0.1, levels: int = 10, mask: Optional[Tensor] = None, seed: int = 0,
+) -> VoxelSample:
+    """Spatially even, deterministic sample of exactly ``m`` point indices
+    per cloud: xyz (B,N,3), optional mask (B,N) bool -> ``VoxelSample``.
+    m >= 1, voxel > 0, 1 <= levels <= 16, N < 2**27; anything else raises
+    ValueError.  The same integers on every backend and in every run.
+
+    Cells.  ``inv = fp32(1) / fp32(voxel)`` is computed on the host; per
+    coordinate ``q = floor(fp32(x * inv))``.  A point is eligible iff it is
+    masked, its three coordinates are finite and -2**20 <= q < 2**20 for all
+    three.  ``c0 = int(q)``; the level-l cell is ``c0 >> l`` (arithmetic
+    shift: negative cells floor), so the grids are nested and level l has
+    edge ``voxel * 2**l``.  A product ``x * inv`` that is a denormal fp32
+    number is unspecified (it may or may not be flushed to zero).
+
+    Tag.  With unsigned 32-bit arithmetic
+      mix(x): x ^= x>>16; x *= 0x85EBCA6B; x ^= x>>13; x *= 0xC2B2AE35; x ^= x>>16
+      key(b) = mix(seed ^ mix(b*0x9E3779B1 + 1)),  h_i = mix(key(b) ^ i)
+    and ``tag_i = (h_i << 32) | i`` as an unsigned 64-bit number.  Two points
+    can share a hash (from about N = 2**16 upward they do); the index makes
+    the order total, all comparisons use the 64 bits.
+
+    Representative and rank.  The representative of an occupied level-l cell
+    is its eligible member with the smallest tag.  A minimum over a union is
+    the minimum of the minima, so a level-l representative also represents
+    its cell at every finer level.  ``rank_i`` counts the levels at which i
+    is a representative (0..levels; -1 for an ineligible point) and
+    ``occupied[l]`` is the number of points with rank >= l + 1.
+
+    Selection.  The eligible points are ordered by (rank descending, tag
+    ascending); the first ``m' = min(m, eligible)`` are taken and returned in
+    ascending index order, padded with -1 up to m.
+
+    Guarantee.  Let l* be the smallest level with ``occupied[l*] <= m'``.
+    Every occupied level-l* cell then contains a selected point, so every
+    eligible point is within ``sqrt(3) * voxel * 2**l*`` of a sample.  If no
+    such level exists (the coarsest grid has more than m' cells) nothing is
+    promised: raise ``levels`` or ``voxel``; ``occupied`` is returned so the
+    caller can see it.
+
+    GPU: csrc/voxel_sample.hip, no sort: hash-table minima per level with
+    integer atomics, an exact radix select of the cut tag and a compaction;
+    10 + levels launches, no host synchronisation, bit-reproducible.  Every
+    probe loop is capped at the table size; should a cap ever be hit, that
+    cloud comes back with count = -1, idx = -1 and rank = -1 instead of a
+    wrong sample.  Not differentiable.  bf16/fp16/fp64 or non-contiguous
+    inputs are converted to contiguous fp32 here.
+
+    The defaults (0.1 m, 10 levels) are untuned guesses at metric driving
+    scenes: nobody has tuned them on real data.
+    """
+    m, inv, levels, seed = reference.voxel_params(m, voxel, levels, seed)
+    if xyz.dim() != 3 or xyz.shape[-1] != 3:
+        raise ValueError(f"voxel_sample needs xyz (B,N,3), got {tuple(xyz.shape)}")
+    B, N = xyz.shape[:2]
+    if not N < (1 << 27):
+        raise ValueError(f"voxel_sample requires N < 2**27, got {N}")
+    if mask is not None:
+        if mask.shape != xyz.shape[:2]:
+            raise ValueError(f"voxel_sample needs mask (B,N), got {tuple(mask.shape)}")
+        mask = mask.detach().bool().contiguous()
+    xyz = xyz.detach().float().contiguous()
+    if _use_hip(xyz) and B > 0 and N > 0:
+        return VoxelSample(*_EXT.voxel_sample(xyz, mask, m, inv, levels, seed))
+    return VoxelSample(*reference.voxel_sample(xyz, m, inv, levels, mask, seed))

@@ -697,3 +697,89 @@ def fit_plane(xyz, mask, thresh, thresh2, cos2, up32, hypotheses, refine_iters, 
         th32 = torch.tensor(thresh, dtype=torch.float32, device=dev)
         return (normal.float(), offset.float(), height, height <= th32, height.abs() <= th32,
                 cnt, best, rounds.int(), ok)
+
+
+# ---------------------------------------------------------------------------
+# Voxel-stratified sampling (absent in the reference): nested grids, hashed tags
+# ---------------------------------------------------------------------------
+
+VOXEL_RANGE = 1 << 20  # cells per axis on either side of zero
+
+
+def voxel_params(m, voxel, levels, seed):
+    """Checks the scalar arguments of ``voxel_sample`` and returns the numbers
+    every backend computes with: m, ``inv = fp32(1) / fp32(voxel)`` as a
+    Python float, levels and the seed as an unsigned 32-bit integer.  Raises
+    ValueError."""
+    try:
+        m, voxel, levels, seed = int(m), float(voxel), int(levels), int(seed)
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"voxel_sample: bad argument: {e}") from None
+    if not m >= 1:
+        raise ValueError(f"voxel_sample requires m >= 1, got {m}")
+    if not (voxel > 0 and math.isfinite(voxel)):
+        raise ValueError(f"voxel_sample requires a finite voxel > 0, got {voxel}")
+    if not 1 <= levels <= 16:
+        raise ValueError(f"voxel_sample requires 1 <= levels <= 16, got {levels}")
+    v32 = torch.tensor(voxel, dtype=torch.float32)
+    inv = float((torch.ones((), dtype=torch.float32) / v32).item())
+    if not (v32.item() > 0 and inv > 0 and math.isfinite(inv)):
+        raise ValueError(f"voxel_sample: 1 / voxel is not a positive fp32 number for voxel = {voxel}")
+    return m, inv, levels, seed & 0xFFFFFFFF
+
+
+def voxel_sample(xyz: Tensor, m: int, inv: float, levels: int, mask: Optional[Tensor], seed: int):
+    """Torch version of ``ops.voxel_sample`` with the prepared numbers of
+    ``voxel_params``: one stable sort by the hash puts the points in tag
+    order, then one stable sort by the packed cell key per level finds the
+    representatives (the first of every key group), and one stable sort by
+    rank makes the cut.  Fixed shapes, no host synchronisation.  Returns idx
+    (B,m) int64, count (B,) int32, rank (B,N) int32, occupied (B,levels)
+    int32."""
+    with torch.no_grad():
+        B, N, _ = xyz.shape
+        dev = xyz.device
+        i64 = dict(dtype=torch.int64, device=dev)
+        L = int(levels)
+        if N == 0:
+            return (torch.full((B, m), -1, **i64), torch.zeros(B, dtype=torch.int32, device=dev),
+                    torch.zeros(B, 0, dtype=torch.int32, device=dev),
+                    torch.zeros(B, L, dtype=torch.int32, device=dev))
+        x = xyz.float()
+        q = torch.floor(x * torch.tensor(inv, dtype=torch.float32, device=dev))
+        el = torch.isfinite(x).all(-1) & (q >= -VOXEL_RANGE).all(-1) & (q < VOXEL_RANGE).all(-1)
+        if mask is not None:
+            el = el & mask
+        f = torch.where(el.unsqueeze(-1), q, torch.zeros_like(q)).long() + VOXEL_RANGE  # biased fields, 21 bits
+        ar = torch.arange(N, **i64)
+        b = torch.arange(B, **i64)
+        kb = _mix32(seed ^ _mix32((_mul32(b, 0x9E3779B1) + 1) & 0xFFFFFFFF))
+        h = _mix32(kb.view(B, 1) ^ ar.view(1, N))
+        order = torch.sort(h, dim=1, stable=True).indices  # tag order: (hash, index) ascending
+        f_t = f.gather(1, order.unsqueeze(-1).expand(B, N, 3))
+        alive = el.gather(1, order)
+        rank_t = alive.long() - 1  # 0 eligible, -1 not
+        occupied = torch.zeros(B, L, **i64)
+        sent = torch.full((), (1 << 63) - 1, **i64)
+        for lv in range(L):
+            g = f_t >> lv  # (c + 2^20) >> l = (c >> l) + 2^(20-l): one code per level-l cell
+            key = torch.where(alive, (g[..., 0] << 42) | (g[..., 1] << 21) | g[..., 2], sent)
+            ks, ki = torch.sort(key, dim=1, stable=True)
+            first = torch.ones_like(alive)
+            first[:, 1:] = ks[:, 1:] != ks[:, :-1]
+            first = first & (ks != sent)
+            alive = torch.zeros_like(alive).scatter_(1, ki, first)
+            rank_t = rank_t + alive.long()
+            occupied[:, lv] = alive.sum(1)
+        n_el = el.sum(1)
+        take = n_el.clamp(max=m)  # m'
+        si = torch.sort(-rank_t, dim=1, stable=True).indices  # rank descending, tag ascending, ineligible last
+        sel_t = torch.zeros_like(alive).scatter_(1, si, ar.view(1, N) < take.view(B, 1))
+        sel = torch.zeros_like(alive).scatter_(1, order, sel_t)
+        rank = torch.zeros(B, N, **i64).scatter_(1, order, rank_t)
+        mm = min(m, N)
+        pos = torch.where(sel, sel.long().cumsum(1) - 1, torch.full((), mm, **i64))
+        out = torch.full((B, mm + 1), -1, **i64).scatter_(1, pos, ar.view(1, N).expand(B, N))
+        idx = torch.full((B, m), -1, **i64)
+        idx[:, :mm] = out[:, :mm]
+        return idx, take.int(), rank.int(), occupied.int()

@@ -38,6 +38,7 @@ SOURCES = [
     "pvraft_amd/csrc/rigid_fit.hip",
     "pvraft_amd/csrc/cluster.hip",
     "pvraft_amd/csrc/plane_fit.hip",
+    "pvraft_amd/csrc/voxel_sample.hip",
 ]
 
 setup(

@@ -35,6 +35,10 @@ def parse_args():
     parser.add_argument("--ground_tilt", help="largest angle between the ground normal and +y (degrees)", default=20.0, type=float)
     parser.add_argument("--ground_iters", help="refinement rounds of the ground fit", default=3, type=int)
     parser.add_argument("--keep_ground", help="KITTI: keep the y < -1.4 points the loader removes by default", action="store_true")
+    parser.add_argument("--sample", help="how the max_points inputs are drawn: the loader's uniform subsample, or ops.voxel_sample on both full clouds (adds sample_cut_* to the report)", default="random", choices=["random", "voxel"])
+    parser.add_argument("--sample_voxel", help="finest cell edge of the voxel sampler (m)", default=0.1, type=float)
+    parser.add_argument("--sample_levels", help="nested grid levels of the voxel sampler", default=10, type=int)
+    parser.add_argument("--sample_seed", help="seed of the voxel sampler's tie-breaking hash", default=0, type=int)
     return parser.parse_args()
 
 
