@@ -1025,6 +1025,91 @@ torch::Tensor pw_fwd(std::vector<torch::Tensor> ws,
   return y;
 }
 
+// Fused data gradient of a pw_fwd stack (csrc/pw_bwd.hip): ReLU mask,
+// point-major transpose and every part's W_i^T @ dpre in one launch.
+// Returns the dx of the wanted parts in order, then dpre (channel-major;
+// dy itself when neither ReLU nor point-major changes it, the slab's row
+// block when a slab is given).
+void launch_pw_bwd(const void**, void**, const int*, const int*, int,
+                   const void*, const void*, void*, long, int, int, long, int,
+                   hipStream_t);
+
+std::vector<torch::Tensor> pw_bwd(torch::Tensor dy,
+                                  c10::optional<torch::Tensor> y,
+                                  std::vector<torch::Tensor> ws,
+                                  std::vector<bool> want, int64_t act,
+                                  bool point_major,
+                                  c10::optional<torch::Tensor> slab,
+                                  int64_t r0) {
+  const int n = (int)ws.size();
+  TORCH_CHECK(n <= 4 && (int)want.size() == n, "pw_bwd: at most 4 parts");
+  TORCH_CHECK(dy.is_cuda() && dy.is_contiguous() && dy.dim() == 3 &&
+              dy.scalar_type() == torch::kBFloat16,
+              "pw_bwd: dy must be contiguous 3-D bf16");
+  const int B = dy.size(0);
+  const int Co = point_major ? dy.size(2) : dy.size(1);
+  const long S = point_major ? dy.size(1) : dy.size(2);
+  TORCH_CHECK(Co >= 1 && Co <= 256, "pw_bwd: Co <= 256");
+  TORCH_CHECK(act == 0 || act == 1, "pw_bwd: act 0 (none) or 1 (relu)");
+  const void* yptr = nullptr;
+  if (act == 1) {
+    TORCH_CHECK(y.has_value() && y->defined() && y->is_cuda() &&
+                y->is_contiguous() && y->scalar_type() == torch::kBFloat16 &&
+                y->sizes() == dy.sizes(),
+                "pw_bwd: relu needs the saved y, shaped like dy");
+    yptr = y->data_ptr();
+  }
+  const void* wp[4];
+  void* dxp[4];
+  int cis[4];
+  int lds[4];
+  std::vector<torch::Tensor> outs;
+  int nw = 0;
+  for (int i = 0; i < n; ++i) {
+    TORCH_CHECK(ws[i].is_cuda() && ws[i].dim() == 2 &&
+                (ws[i].size(1) == 1 || ws[i].stride(1) == 1) &&
+                (ws[i].size(0) == 1 || ws[i].stride(0) >= ws[i].size(1)) &&
+                ws[i].scalar_type() == torch::kBFloat16,
+                "w must be (Co,Ci) bf16 with contiguous rows");
+    TORCH_CHECK(ws[i].size(0) == Co, "pw_bwd: w rows != Co");
+    TORCH_CHECK(ws[i].size(1) >= 1 && ws[i].size(1) <= 224, "pw_bwd: Ci <= 224");
+    if (!want[i]) continue;
+    const long Ci = ws[i].size(1);
+    auto dx = torch::empty({B, Ci, S}, dy.options());
+    wp[nw] = ws[i].data_ptr();
+    dxp[nw] = dx.data_ptr();
+    cis[nw] = (int)Ci;
+    lds[nw] = ws[i].size(0) == 1 ? (int)Ci : (int)ws[i].stride(0);
+    outs.push_back(dx);
+    ++nw;
+  }
+  torch::Tensor dpre = dy;
+  void* dptr = nullptr;
+  long dbs = 0;
+  if (slab.has_value() && slab->defined()) {
+    auto& sl = *slab;
+    TORCH_CHECK(act == 0 && !point_major,
+                "pw_bwd: slab output needs act=none and channel-major dy");
+    TORCH_CHECK(sl.is_cuda() && sl.dim() == 3 && sl.size(0) == B &&
+                sl.size(2) == S && sl.scalar_type() == torch::kBFloat16 &&
+                sl.stride(2) == 1 && sl.stride(1) == S &&
+                r0 >= 0 && r0 + Co <= sl.size(1),
+                "pw_bwd: slab must be (B,Ctot,S) bf16 with contiguous rows");
+    dpre = sl.narrow(1, r0, Co);
+    dptr = dpre.data_ptr();
+    dbs = sl.stride(0);
+  } else if (act == 1 || point_major) {
+    dpre = torch::empty({B, (long)Co, S}, dy.options());
+    dptr = dpre.data_ptr();
+    dbs = (long)Co * S;
+  }
+  if (B > 0 && S > 0 && (nw > 0 || dptr != nullptr))
+    launch_pw_bwd(wp, dxp, cis, lds, nw, dy.data_ptr(), yptr, dptr, dbs, B, Co,
+                  S, point_major ? 1 : 0, stream());
+  outs.push_back(dpre);
+  return outs;
+}
+
 // Batched deferred weight gradients: many (dy, x) -> dW problems in ONE
 // kernel launch, each ACCUMULATED into its weight's existing fp32 grad
 // buffer (no per-call zero-fill, no autograd accumulate-add).  ~180 such
@@ -1777,6 +1862,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("pw_fwd", &pw_fwd, pybind11::arg("ws"), pybind11::arg("xs"),
         pybind11::arg("bias"), pybind11::arg("addend"), pybind11::arg("act"),
         pybind11::arg("point_major") = false);
+  m.def("pw_bwd", &pw_bwd, pybind11::arg("dy"), pybind11::arg("y"),
+        pybind11::arg("ws"), pybind11::arg("want"), pybind11::arg("act"),
+        pybind11::arg("point_major") = false,
+        pybind11::arg("slab") = pybind11::none(), pybind11::arg("r0") = 0);
   m.def("batched_transpose", &batched_transpose);
   m.def("group_norm_act_fwd", &group_norm_act_fwd);
   m.def("group_norm_act_bwd", &group_norm_act_bwd);

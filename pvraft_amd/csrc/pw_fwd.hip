@@ -18,10 +18,11 @@
 // of one batch's output and ALL Co rows (template NRF = row fragments,
 // statically indexed accumulators -- dynamic indexing would spill to
 // scratch).  Per part, the (Co x Ci) weight and the (Ci x 64) activation
-// tile are staged in dynamic LDS (the activation transposed on the way
-// in: x is channel-major, the B fragment wants k-contiguous columns),
-// zero-padded to a 32-multiple k so ragged Ci (61, 3, 81...) needs no
-// edge cases.  bf16 operands, fp32 accumulate
+// tile are staged in dynamic LDS (x is channel-major and the B fragment
+// wants k-contiguous columns: the tile is stored as it lies in memory and
+// read back transposed, pw_stage.h), zero-padded to a 32-multiple k so
+// ragged Ci (61, 3, 81...) needs no edge cases.  bf16 operands, fp32
+// accumulate
 // (v_mfma_f32_16x16x32_bf16), bf16 store.
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
@@ -29,6 +30,7 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "pw_stage.h"
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
@@ -50,7 +52,16 @@ struct PwFwdPart {
   int ld;         // >= ci: a column slice of a wider weight needs no copy
 };
 
-template <int NRF, int TC>
+// CLASSIC selects the operand staging.  false (default): pw_stage.h -- the
+// activation tile lies in LDS as in memory, (cip, TC) rows moved 16 bytes at
+// a time, and the k-contiguous B fragment comes from the transposed LDS
+// read in the NATURAL slot order (pw_stage.h), next to the plain 16-byte
+// weight-row read.  true (PVRAFT_PW_STAGE=classic): the tile is transposed
+// on the way in with 2-byte LDS stores.  Both put the same product into the
+// same slot of every MFMA, so y is bit-equal (tests/test_gpu_pw_stage.py);
+// the conflict-free permuted slot order of pw_stage.h is NOT (measured: last
+// bit of y differs), so the forward does not use it.
+template <int NRF, int TC, bool CLASSIC>
 __global__ __launch_bounds__(PF_THREADS) void pw_fwd_kernel(
     PwFwdPart p0, PwFwdPart p1, PwFwdPart p2, PwFwdPart p3, int nparts,
     const float *__restrict__ bias,   // (Co) fp32 or null
@@ -61,9 +72,11 @@ __global__ __launch_bounds__(PF_THREADS) void pw_fwd_kernel(
   constexpr int COL16 = TC / 16;        // column tiles per WG
   constexpr int RFG = 4 / COL16;        // wave groups along rows
   constexpr int NRF_PER = (NRF + RFG - 1) / RFG;  // row frags per wave
-  extern __shared__ __hip_bfloat16 smem[];
+  extern __shared__ __attribute__((aligned(16))) __hip_bfloat16 smem[];
   __hip_bfloat16 *s_w = smem;                       // (NRF*16, pitch)
-  __hip_bfloat16 *s_x = smem + (long)NRF * 16 * pitch;  // (TC, pitch)
+  // classic: (TC, pitch) transposed; else (cip, pws_tr_pitch(TC)) as stored
+  __hip_bfloat16 *s_x = smem + (long)NRF * 16 * pitch;
+  constexpr int pitch_x = pws_tr_pitch(TC);
 
   const int b = blockIdx.z;
   const long s0 = (long)blockIdx.x * TC;
@@ -89,6 +102,34 @@ __global__ __launch_bounds__(PF_THREADS) void pw_fwd_kernel(
     const __hip_bfloat16 *x =
         (const __hip_bfloat16 *)pp.x + (long)b * ci * S;
     __syncthreads();
+    if constexpr (!CLASSIC) {
+      // W rows k-contiguous, the activation tile as it lies in memory;
+      // both zero-padded to cip (x rows) / NRF*16 (W rows).  vec = true
+      // throughout: nothing but src is touched, and a 16-byte global load
+      // needs no alignment, so ragged S and odd weight pitches move whole
+      // in-range chunks as vectors too (only chunks cut by the tile edge or
+      // by Ci go element by element)
+      pws_stage_rows(s_w, pitch, w, ld, Co, NRF * 16, cip, ci, true, nullptr,
+                     nullptr, 0);
+      const int tcv = (S - s0) < TC ? (int)(S - s0) : TC;
+      pws_stage_rows(s_x, pitch_x, x + s0, S, ci, cip, TC, tcv, true, nullptr,
+                     nullptr, 0);
+      __syncthreads();
+      for (int kb = 0; kb < cip; kb += 32) {
+        const bf16x8 bfrag = pws_tr_frag<true>(s_x, pitch_x, kb, ct * 16, lane);
+#pragma unroll
+        for (int rf = 0; rf < NRF_PER; ++rf) {
+          if (rf0 + rf < NRF) {  // wave-uniform guard (keeps the unroll)
+            const bf16x8 afrag = *(const bf16x8 *)&s_w[
+                (long)((rf0 + rf) * 16 + (lane & 15)) * pitch + kb +
+                (lane >> 4) * 8];
+            acc[rf] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                afrag, bfrag, acc[rf], 0, 0, 0);
+          }
+        }
+      }
+      continue;
+    }
     // stage W rows (k-contiguous, zero-padded in both dims)
     for (int i = threadIdx.x; i < NRF * 16 * (cip / 8); i += PF_THREADS) {
       const int r = i / (cip / 8);
@@ -215,15 +256,27 @@ void launch_pw_fwd(const void **ws, const void **xs, const int *cis,
     if ((long)B * ((S + 63) / 64) < 512) tc = 32;
     if ((long)B * ((S + 31) / 32) < 512) tc = 16;
   }
-#define PF_LAUNCH_T(NRF, TC)                                                  \
+  // read per launch: the A/B run and the bit-equality test flip it
+  const char *stage_env = getenv("PVRAFT_PW_STAGE");
+  const bool classic_stage = stage_env && stage_env[0] == 'c';
+  // the weight tile holds the kernel's NRF*16 rows (the default case
+  // rounds nrf up to 16)
+#define PF_LAUNCH_TS(NRF, TC, CL)                                             \
   do {                                                                        \
     const dim3 grid((unsigned)((S + TC - 1) / TC), 1, B);                     \
+    const size_t x_elems = CL ? (size_t)TC * pitch                            \
+                              : (size_t)cip_max * pws_tr_pitch(TC);           \
     const size_t shmem =                                                      \
-        (size_t)(nrf * 16 + TC) * pitch * sizeof(__hip_bfloat16);             \
-    hipLaunchKernelGGL((pw_fwd_kernel<NRF, TC>), grid, dim3(PF_THREADS),      \
+        ((size_t)NRF * 16 * pitch + x_elems) * sizeof(__hip_bfloat16);        \
+    hipLaunchKernelGGL((pw_fwd_kernel<NRF, TC, CL>), grid, dim3(PF_THREADS),  \
                        shmem, stream, p[0], p[1], p[2], p[3], nparts, bias,   \
                        addend, addend_bstride, addend_fp32,                   \
                        (__hip_bfloat16 *)y, Co, S, act, pitch, point_major);  \
+  } while (0)
+#define PF_LAUNCH_T(NRF, TC)                                                  \
+  do {                                                                        \
+    if (classic_stage) PF_LAUNCH_TS(NRF, TC, true);                           \
+    else PF_LAUNCH_TS(NRF, TC, false);                                        \
   } while (0)
 #define PF_LAUNCH(NRF)                                                        \
   do {                                                                        \
@@ -245,4 +298,5 @@ void launch_pw_fwd(const void **ws, const void **xs, const int *cis,
   }
 #undef PF_LAUNCH
 #undef PF_LAUNCH_T
+#undef PF_LAUNCH_TS
 }

@@ -240,6 +240,140 @@ def _cast_cached(t: Tensor, dt) -> Tensor:
     return ent[1]
 
 
+def _pw_bwd_fused_ok(dy: Tensor, ws) -> bool:
+    """The fused data-gradient kernel (csrc/pw_bwd.hip) takes this backward:
+    CUDA bf16 within the kernel's limits.  ``PVRAFT_PW_BWD=classic`` keeps
+    the composed threshold_backward / transpose / bmm path."""
+    if not (dy.is_cuda and dy.dtype == torch.bfloat16 and dy.dim() == 3):
+        return False
+    if os.environ.get("PVRAFT_PW_BWD", "") == "classic":
+        return False
+    if len(ws) > 4 or ws[0].shape[0] > 256 or dy.numel() == 0:
+        return False
+    for w in ws:
+        if not (
+            w.dtype == torch.bfloat16
+            and w.dim() == 2
+            and 1 <= w.shape[1] <= 224
+            and (w.shape[1] == 1 or w.stride(1) == 1)
+            and (w.shape[0] == 1 or w.stride(0) >= w.shape[1])
+        ):
+            return False
+    # skinny-k giant-S GEMMs stay on hipBLASLt, as in the forward
+    s = max(dy.shape[1], dy.shape[2])
+    if s > 100_000 and min(w.shape[1] for w in ws) < 16:
+        return False
+    return True
+
+
+# Which way _RowSplit.backward went.  The hand-off to the fast path rides on
+# a tensor attribute (_pw_slab) that any op between row_split() and
+# pw_fused() silently drops; the backward then concatenates, which is
+# correct but costs the launches again -- these two counts are the only
+# place where that shows (one dict increment per GRU iteration).
+ROWSPLIT_STATS = {"fast": 0, "cat": 0}
+
+
+class _SlabHolder:
+    """Shared gradient buffer of one row_split(): the consumers of the two
+    row blocks write their addend gradients straight into it."""
+
+    def __init__(self, ctot: int):
+        self.ctot = ctot
+        self.buf = None
+        self.filled = set()
+
+    def rows(self, r0: int, dy: Tensor):
+        """(buffer, first row) for the consumer of the block starting at
+        row ``r0``; allocates on first use (under hipGraph capture this is
+        an ordinary captured temporary)."""
+        B, _co, S = dy.shape
+        if self.buf is None or self.buf.shape != (B, self.ctot, S) \
+                or self.buf.device != dy.device:
+            self.buf = torch.empty((B, self.ctot, S), dtype=dy.dtype,
+                                   device=dy.device)
+            self.filled = set()
+        self.filled.add(r0)
+        return self.buf, r0
+
+
+def _is_block_of(g: Tensor, buf: Tensor, lo: int, hi: int) -> bool:
+    ref = buf[:, lo:hi]
+    return (
+        g.dtype == buf.dtype
+        and g.device == buf.device
+        and g.shape == ref.shape
+        and g.stride() == ref.stride()
+        and g.data_ptr() == ref.data_ptr()
+    )
+
+
+class _RowSplit(torch.autograd.Function):
+    """m -> (m[:, :a], m[:, a:]) whose backward receives BOTH slice
+    gradients: autograd's own slicing turns each into a zero-filled full
+    tensor plus a strided copy and adds the two.  When both gradients
+    already are the two row blocks of the holder's buffer (written there by
+    pw_bwd) the gradient of m is that buffer -- no launch; anything else is
+    one cat (or a zero-pad for a missing side)."""
+
+    @staticmethod
+    def forward(ctx, m: Tensor, a: int, holder):
+        ctx.a = a
+        ctx.holder = holder
+        ctx.m_meta = (m.shape, m.dtype, m.device)
+        return m[:, :a], m[:, a:]
+
+    @staticmethod
+    def backward(ctx, g1, g2):
+        a = ctx.a
+        shape, dtype, device = ctx.m_meta
+        holder = ctx.holder
+        buf = holder.buf if holder is not None else None
+        filled = holder.filled if holder is not None else ()
+        if holder is not None:
+            holder.buf = None
+            holder.filled = set()
+        if (
+            buf is not None
+            and g1 is not None
+            and g2 is not None
+            and tuple(buf.shape) == tuple(shape)
+            and 0 in filled
+            and a in filled
+            and _is_block_of(g1, buf, 0, a)
+            and _is_block_of(g2, buf, a, shape[1])
+        ):
+            ROWSPLIT_STATS["fast"] += 1
+            return buf, None, None
+        ROWSPLIT_STATS["cat"] += 1
+        if g1 is None and g2 is None:
+            return None, None, None
+        if g1 is None:
+            g1 = g2.new_zeros((shape[0], a) + tuple(shape[2:]))
+        if g2 is None:
+            g2 = g1.new_zeros((shape[0], shape[1] - a) + tuple(shape[2:]))
+        return torch.cat([g1, g2], dim=1), None, None
+
+
+def row_split(m: Tensor, a: int):
+    """(m[:, :a], m[:, a:]) as views, for use as pw_fused addends; see
+    _RowSplit.  ``PVRAFT_PW_ROWSPLIT=classic`` turns the shared-buffer fast
+    path off (the backward then always concatenates)."""
+    holder = None
+    if (
+        m.is_cuda
+        and m.dim() == 3
+        and m.dtype == torch.bfloat16
+        and os.environ.get("PVRAFT_PW_ROWSPLIT", "") != "classic"
+    ):
+        holder = _SlabHolder(m.shape[1])
+    lo, hi = _RowSplit.apply(m, a, holder)
+    if holder is not None:
+        lo._pw_slab = (holder, 0)
+        hi._pw_slab = (holder, a)
+    return lo, hi
+
+
 class _PwMatmul(torch.autograd.Function):
     """y (B, Co, S) = w (Co, Ci) @ x (B, Ci, S) with split-K backward.
 
@@ -273,11 +407,14 @@ class _PwMatmul(torch.autograd.Function):
         wc, x = ctx.saved_tensors
         w_dtype, b_dtype = ctx.grad_dtypes
         dy = dy.contiguous()
-        dx = (
-            torch.bmm(wc.t().unsqueeze(0).expand(dy.shape[0], -1, -1), dy)
-            if ctx.needs_input_grad[1]
-            else None
-        )
+        if not ctx.needs_input_grad[1]:
+            dx = None
+        elif wc.dim() == 2 and dy.dim() == 3 and _pw_bwd_fused_ok(dy, (wc,)):
+            from pvraft_amd import _C
+
+            dx = _C.pw_bwd(dy, None, [wc], [True], 0)[0]
+        else:
+            dx = torch.bmm(wc.t().unsqueeze(0).expand(dy.shape[0], -1, -1), dy)
         dw = None
         dbias = None
         need_w = ctx.needs_input_grad[0]
@@ -346,6 +483,7 @@ class _PwFused(torch.autograd.Function):
         ctx.save_for_backward(*ws, *xs, y)
         ctx.conf = (act_id, targets, p)
         ctx.point_major = point_major
+        ctx.slab = conf[5] if len(conf) > 5 else None
         ctx.has_bias = bias is not None
         ctx.has_addend = addend is not None
         ctx.w_dtypes = tuple(w.dtype for w in wx[:p])
@@ -357,21 +495,44 @@ class _PwFused(torch.autograd.Function):
         saved = ctx.saved_tensors
         ws, xs, y = saved[:p], saved[p : 2 * p], saved[2 * p]
         dy = dy.contiguous()
-        dpre = (
-            torch.ops.aten.threshold_backward(dy, y, 0) if act_id == 1 else dy
-        )
-        if ctx.point_major:
-            # (B, S, Co) -> (B, Co, S) once; dx / wgrad proceed as usual
+        want = [bool(ctx.needs_input_grad[3 + p + i]) for i in range(p)]
+        if _pw_bwd_fused_ok(dy, ws):
+            # one launch: ReLU mask, point-major transpose and every wanted
+            # part's W_i^T @ dpre (csrc/pw_bwd.hip)
             from pvraft_amd import _C
 
-            dpre = _C.batched_transpose(dpre)
-        d_addend = dpre if ctx.has_addend else None
-        dxs = [
-            torch.bmm(w.t().unsqueeze(0).expand(dpre.shape[0], -1, -1), dpre)
-            if ctx.needs_input_grad[3 + p + i]
-            else None
-            for i, w in enumerate(ws)
-        ]
+            slab, r0 = None, 0
+            if (
+                ctx.slab is not None
+                and act_id == 0
+                and not ctx.point_major
+                and ctx.needs_input_grad[1]
+            ):
+                slab, r0 = ctx.slab[0].rows(ctx.slab[1], dy)
+            outs = _C.pw_bwd(dy, y if act_id == 1 else None, list(ws), want,
+                             act_id, ctx.point_major, slab, r0)
+            it = iter(outs[:-1])
+            dxs = [next(it) if wnt else None for wnt in want]
+            # with a slab, outs[-1] is its row block (the addend gradient);
+            # the wgrad queue keeps the contiguous dy, which it equals
+            d_addend = outs[-1] if ctx.has_addend else None
+            dpre = dy if slab is not None else outs[-1]
+        else:
+            dpre = (
+                torch.ops.aten.threshold_backward(dy, y, 0) if act_id == 1 else dy
+            )
+            if ctx.point_major:
+                # (B, S, Co) -> (B, Co, S) once; dx / wgrad proceed as usual
+                from pvraft_amd import _C
+
+                dpre = _C.batched_transpose(dpre)
+            d_addend = dpre if ctx.has_addend else None
+            dxs = [
+                torch.bmm(w.t().unsqueeze(0).expand(dpre.shape[0], -1, -1), dpre)
+                if wnt
+                else None
+                for wnt, w in zip(want, ws)
+            ]
         dws = [None] * p
         d_bias = None
         need_bias = ctx.has_bias and ctx.needs_input_grad[0]
@@ -449,8 +610,12 @@ def pw_fused(parts, bias=None, bias_target=None, addend=None, act="none",
             x.to(dt).contiguous() for _w, x, _t in parts
         )
         b = bias.float() if bias is not None and bias.dtype != torch.float32 else bias
+        # a row_split() block as addend: its gradient goes straight into
+        # the split's shared buffer
+        slab = getattr(addend, "_pw_slab", None) if addend is not None else None
         return _PwFused.apply(
-            b, addend, (act_id, targets, p, dt, bool(out_point_major)), *wx)
+            b, addend, (act_id, targets, p, dt, bool(out_point_major), slab),
+            *wx)
     out = None
     for i, (w, x, tgt) in enumerate(parts):
         b = bias if i == 0 else None

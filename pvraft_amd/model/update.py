@@ -194,7 +194,7 @@ class ConvGRU(nn.Module):
         fused HIP kernels per direction (ops.gru_zr / ops.gru_q)."""
         from pvraft_amd import ops
 
-        from .pointwise import pw_fused
+        from .pointwise import pw_fused, row_split
 
         if gw is None:
             gw = self.gate_weights([p.shape[1] for p in x_parts])
@@ -215,11 +215,12 @@ class ConvGRU(nn.Module):
             )
         # gate preactivations: hidden-operand GEMM + the matching slice of
         # m, again one kernel each
+        m_zr, m_q = row_split(m, 2 * hd)
         pre_zr = pw_fused([(gw["zr_h"], h, gw["t_zr_h"])], bias=gw["b_zr"],
-                          bias_target=gw["t_b_zr"], addend=m[:, : 2 * hd])
+                          bias_target=gw["t_b_zr"], addend=m_zr)
         z, rh = ops.gru_zr(pre_zr, h)
         pre_q = pw_fused([(gw["q_h"], rh, gw["t_q_h"])], bias=gw["b_q"],
-                         bias_target=gw["b_q"], addend=m[:, 2 * hd :])
+                         bias_target=gw["b_q"], addend=m_q)
         return ops.gru_q(pre_q, z, h)
 
 

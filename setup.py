@@ -27,6 +27,7 @@ SOURCES = [
     "pvraft_amd/csrc/cast_pack.hip",
     "pvraft_amd/csrc/pw_wgrad.hip",
     "pvraft_amd/csrc/pw_fwd.hip",
+    "pvraft_amd/csrc/pw_bwd.hip",
     "pvraft_amd/csrc/transpose.hip",
     "pvraft_amd/csrc/pv_corr_fused.hip",
     "pvraft_amd/csrc/topk_rows.hip",
