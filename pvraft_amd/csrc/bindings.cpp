@@ -1298,6 +1298,54 @@ std::vector<torch::Tensor> corr_topk(torch::Tensor f1t, torch::Tensor f2t,
   return {out_v, out_i};
 }
 
+void launch_corr_grad_expand(const float*, const int*, void*, long, int, int,
+                             float, bool, hipStream_t);
+void launch_corr_gather_xyz(const int*, const float*, float*, int, long, int,
+                            hipStream_t);
+
+// g (B,N,K) fp32, idx (B,N,K) i32 -> dense (B,N,M) bf16 / fp32 with
+// round(g * scale) at idx and zeros elsewhere; every element stored once
+// (csrc/corr_bwd.hip).  The row image lives in LDS: M * itemsize <= 64 KB.
+torch::Tensor corr_grad_expand(torch::Tensor g, torch::Tensor idx,
+                               double scale, int64_t M, bool bf16) {
+  check_f32(g, "g");
+  TORCH_CHECK(g.dim() == 3, "g must be (B, N, K)");
+  TORCH_CHECK(idx.is_cuda() && idx.is_contiguous() &&
+              idx.scalar_type() == torch::kInt32 && idx.sizes() == g.sizes(),
+              "idx must be contiguous int32 of g's shape");
+  TORCH_CHECK(idx.device() == g.device(), "g and idx on different devices");
+  TORCH_CHECK(M >= 1 && M * (bf16 ? 2 : 4) <= 64 * 1024,
+              "row image limited to 64 KB");
+  const long B = g.size(0), N = g.size(1);
+  TORCH_CHECK(B * N < (1L << 31), "too many rows");
+  auto out = torch::empty(
+      {B, N, M}, g.options().dtype(bf16 ? torch::kBFloat16 : torch::kFloat32));
+  launch_corr_grad_expand(g.data_ptr<float>(), idx.data_ptr<int>(),
+                          out.data_ptr(), B * N, (int)g.size(2), (int)M,
+                          (float)scale, bf16, stream());
+  return out;
+}
+
+// idx (B,N,K) i32, xyz2 (B,M,3) fp32 -> xyz2 rows at idx, (B,N,K,3) fp32
+torch::Tensor corr_gather_xyz(torch::Tensor idx, torch::Tensor xyz2) {
+  check_f32(xyz2, "xyz2");
+  TORCH_CHECK(idx.is_cuda() && idx.is_contiguous() && idx.dim() == 3 &&
+              idx.scalar_type() == torch::kInt32,
+              "idx must be contiguous (B, N, K) int32");
+  TORCH_CHECK(xyz2.dim() == 3 && xyz2.size(2) == 3 &&
+              xyz2.size(0) == idx.size(0) && xyz2.size(1) >= 1,
+              "xyz2 must be (B, M, 3)");
+  TORCH_CHECK(idx.device() == xyz2.device(),
+              "idx and xyz2 on different devices");
+  const long B = idx.size(0), N = idx.size(1), K = idx.size(2);
+  TORCH_CHECK((B * N * K + 1023) / 1024 < (1L << 31), "too many entries");
+  auto out = torch::empty({B, N, K, 3}, xyz2.options());
+  launch_corr_gather_xyz(idx.data_ptr<int>(), xyz2.data_ptr<float>(),
+                         out.data_ptr<float>(), (int)B, N * K,
+                         (int)xyz2.size(1), stream());
+  return out;
+}
+
 // vals (R, M) fp32 -> top-K largest per row: values (R, K), idx (R, K)
 std::vector<torch::Tensor> topk_rows(torch::Tensor vals, int64_t K) {
   check_f32(vals, "vals");
@@ -1849,6 +1897,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("flow_smooth_bwd", &flow_smooth_bwd);
   m.def("topk_rows", &topk_rows);
   m.def("corr_topk", &corr_topk);
+  m.def("corr_grad_expand", &corr_grad_expand);
+  m.def("corr_gather_xyz", &corr_gather_xyz);
   m.def("seq_loss_fwd", &seq_loss_fwd);
   m.def("seq_loss_bwd", &seq_loss_bwd);
   m.def("gru_zr_fwd", &gru_zr_fwd);

@@ -73,7 +73,10 @@ class CorrBlock(nn.Module):
 
     def build(self, fmap1: Tensor, fmap2: Tensor, xyz2: Tensor) -> CorrField:
         """Compute the truncated correlation field (once per pair)."""
-        corr, _idx, txyz = ops.corr_truncate(fmap1, fmap2, xyz2, self.truncate_k)
+        # the index is not used here: take it as the kernels made it
+        corr, _idx, txyz = ops.corr_truncate(
+            fmap1, fmap2, xyz2, self.truncate_k, index_dtype=torch.int32
+        )
         return CorrField(corr=corr, xyz=txyz)
 
     def forward(self, field: CorrField, coords: Tensor) -> Tensor:

@@ -662,13 +662,19 @@ class _CorrTruncate(torch.autograd.Function):
     top-K indices:
         d f1[:, n]  = scale * sum_k g[n, k] * f2[:, idx[n, k]]
         d f2[:, m] += scale * sum_{n,k: idx=m} g[n, k] * f1[:, n]
-    which is O(N*K*C) instead of O(N*M*C).
+    which is O(N*K*C) instead of O(N*M*C).  (As executed: the sparse
+    gradient is expanded to a dense (B, N, M) matrix, one pass of
+    corr_grad_expand, and both sums run as dense MFMA GEMMs over it.)
     """
 
     CHUNK = 2048
+    # corr_grad_expand keeps one row of the dense gradient in LDS
+    EXPAND_ROW_BYTES = 64 * 1024
 
     @staticmethod
-    def forward(ctx, fmap1: Tensor, fmap2: Tensor, xyz2: Tensor, truncate_k: int):
+    def forward(ctx, fmap1: Tensor, fmap2: Tensor, xyz2: Tensor, truncate_k: int,
+                index_dtype: torch.dtype = torch.int64):
+        classic = corr_bwd_classic()
         # accumulation stays fp32 everywhere (selection quality follows the
         # reference, corr.py:95-99): the fused MFMA kernel accumulates fp32
         # from bf16 operands; the fp32 fallback disables autocast so the
@@ -689,12 +695,17 @@ class _CorrTruncate(torch.autograd.Function):
                 K = min(truncate_k, M)
                 f1t = _EXT.batched_transpose(fmap1.contiguous())
                 f2t = _EXT.batched_transpose(fmap2.contiguous())
-                corr, idx32 = _EXT.corr_topk(f1t, f2t, K)
-                idx = idx32.long()
+                corr, idx = _EXT.corr_topk(f1t, f2t, K)
                 B, _, N = fmap1.shape
-                txyz = xyz2.gather(
-                    1, idx.reshape(B, N * K).unsqueeze(-1).expand(B, N * K, 3)
-                ).view(B, N, K, 3)
+                if classic or xyz2.dtype != torch.float32:
+                    idx = idx.long()
+                    txyz = xyz2.gather(
+                        1, idx.reshape(B, N * K).unsqueeze(-1).expand(B, N * K, 3)
+                    ).view(B, N, K, 3)
+                else:
+                    # int32 indices straight into the row gather and, saved,
+                    # into the backward (csrc/corr_bwd.hip)
+                    txyz = _EXT.corr_gather_xyz(idx, xyz2.contiguous())
             elif fmap1.is_cuda and M <= 8192 and _load_ext() is not None:
                 corr, idx, txyz = _CorrTruncate._gpu_forward(
                     fmap1.float(), fmap2.float(), xyz2, truncate_k
@@ -710,7 +721,10 @@ class _CorrTruncate(torch.autograd.Function):
         ctx.bf16_bwd = fmap1.is_cuda and (
             torch.is_autocast_enabled() or fmap1.dtype == torch.bfloat16
         )
-        return corr, idx, txyz
+        # int64 unless the caller takes the kernels' int32 as it is; an
+        # index that is already int64 is never narrowed
+        idx_out = idx.long() if index_dtype == torch.int64 else idx
+        return corr, idx_out, txyz
 
     @staticmethod
     def _gpu_forward(fmap1: Tensor, fmap2: Tensor, xyz2: Tensor, truncate_k: int):
@@ -730,10 +744,14 @@ class _CorrTruncate(torch.autograd.Function):
             n_rows = c.shape[1]
             v, i = _EXT.topk_rows(c.reshape(B * n_rows, M), K)
             vals.append(v.view(B, n_rows, K))
-            idxs.append(i.view(B, n_rows, K).long())
+            idxs.append(i.view(B, n_rows, K))
         corr = torch.cat(vals, dim=1)
         idx = torch.cat(idxs, dim=1)
-        txyz = xyz2.gather(1, idx.reshape(B, N * K).unsqueeze(-1).expand(B, N * K, 3)).view(B, N, K, 3)
+        if corr_bwd_classic() or xyz2.dtype != torch.float32:
+            idx = idx.long()
+            txyz = xyz2.gather(1, idx.reshape(B, N * K).unsqueeze(-1).expand(B, N * K, 3)).view(B, N, K, 3)
+        else:
+            txyz = _EXT.corr_gather_xyz(idx, xyz2.contiguous())
         return corr, idx, txyz
 
     @staticmethod
@@ -746,28 +764,60 @@ class _CorrTruncate(torch.autograd.Function):
         # expands to a dense (B, N, M) buffer with a CONFLICT-FREE scatter
         # (no atomics), and both fmap gradients become plain rocBLAS GEMMs.
         dt = torch.bfloat16 if ctx.bf16_bwd else g_corr.dtype
-        gfull = torch.zeros(B, N, M, dtype=dt, device=g_corr.device)
-        gfull.scatter_(2, idx, (g_corr * scale).to(dt))
         f1 = fmap1.to(dt)
         f2 = fmap2.to(dt)
+        if (
+            g_corr.is_cuda
+            and not corr_bwd_classic()
+            and dt in (torch.bfloat16, torch.float32)
+            and M * dt.itemsize <= _CorrTruncate.EXPAND_ROW_BYTES
+            and _load_ext() is not None
+        ):
+            # one pass writes every element of the dense matrix once
+            # (csrc/corr_bwd.hip); the g1 GEMM reads the same buffer as a
+            # transposed operand instead of a transposed copy (in the step
+            # 100 us against 82 + 167 us at the flagship shape; multiplying
+            # by the point-major fmap2 and transposing the result gave the
+            # same step time, see profiles/README.md)
+            gfull = _EXT.corr_grad_expand(
+                g_corr.float().contiguous(), idx.to(torch.int32), scale, M,
+                dt == torch.bfloat16,
+            )
+            g1 = torch.bmm(f2, gfull.transpose(1, 2)).float()  # (B,C,N)
+            g2 = torch.bmm(f1, gfull).float()  # (B,C,M)
+            return g1, g2, None, None, None
+        gfull = torch.zeros(B, N, M, dtype=dt, device=g_corr.device)
+        gfull.scatter_(2, idx.long(), (g_corr * scale).to(dt))
         if gfull.is_cuda and _load_ext() is not None:
             gfull_t = _EXT.batched_transpose(gfull)
         else:
             gfull_t = gfull.transpose(1, 2).contiguous()
         g1 = torch.bmm(f2, gfull_t).float()  # (B,C,N)
         g2 = torch.bmm(f1, gfull).float()  # (B,C,M)
-        return g1, g2, None, None
+        return g1, g2, None, None, None
 
 
-def corr_truncate(fmap1: Tensor, fmap2: Tensor, xyz2: Tensor, truncate_k: int):
+def corr_bwd_classic() -> bool:
+    """PVRAFT_CORR_BWD=classic (read per call) restores the composed
+    truncated-correlation path: int64 indices + ATen gather in the forward,
+    zeros + scatter_ + transposed copy in the backward."""
+    return os.environ.get("PVRAFT_CORR_BWD", "") == "classic"
+
+
+def corr_truncate(fmap1: Tensor, fmap2: Tensor, xyz2: Tensor, truncate_k: int,
+                  index_dtype: torch.dtype = torch.int64):
     """(B,C,N),(B,C,M),(B,M,3) -> corr (B,N,K), idx (B,N,K), xyz (B,N,K,3).
 
     bf16 inputs (autocast) take the fused MFMA GEMM + streaming top-K
     kernel; fp32 falls back to the chunked rocBLAS bmm + topk_rows path.
-    Values are always fp32 accumulate.
+    Values are always fp32 accumulate.  ``index_dtype=torch.int32`` hands
+    out the kernels' own indices where the path has them, for callers that
+    do not need ``idx`` as int64 (the conversion is a 64 MB write at the
+    flagship shape); the reference paths return their int64 index as it
+    is.
     """
     if fmap1.is_cuda and os.environ.get("PVRAFT_REF_OPS", "0") != "1":
-        return _CorrTruncate.apply(fmap1, fmap2, xyz2, truncate_k)
+        return _CorrTruncate.apply(fmap1, fmap2, xyz2, truncate_k, index_dtype)
     return reference.corr_truncate(fmap1.float(), fmap2.float(), xyz2, truncate_k)
 
 
