@@ -58,6 +58,12 @@ void launch_voxel_sample(const float*, const unsigned char*, unsigned long long*
 int voxel_sample_block();
 int voxel_sample_scan();
 long voxel_sample_meta();
+void launch_noise_filter(const float*, const unsigned char*, unsigned long long*,
+                         int*, int*, float*, int*, int*, double*, unsigned char*,
+                         int*, float*, double*, unsigned char*, int, int, int,
+                         float, float, int, int, double, hipStream_t);
+int noise_filter_block();
+int noise_filter_scan();
 void launch_morton_keys(const float*, const float*, const float*, long*,
                         int, long, hipStream_t);
 void launch_gather_edge_fwd(const void*, const int*, const float*, void*,
@@ -1875,7 +1881,72 @@ std::vector<torch::Tensor> voxel_sample(torch::Tensor xyz,
   return {idx, count, rank, occ};
 }
 
+// Noise filter (csrc/noise_filter.hip).  xyz (B,N,3) f32, optional mask (B,N)
+// bool, inv = fp32(1 / radius) and r2 = fp32(radius)^2 from the caller so every
+// backend computes with the same numbers -> {keep (B,N) bool, count (B,N) i32,
+// mean_dist (B,N) f32, stats (B,3) f64 = mean, std, threshold, ok (B) bool}.
+// 9 launches, no host synchronisation.  The workspaces are torch allocations
+// of this call; every word is written before it is read.
+std::vector<torch::Tensor> noise_filter(torch::Tensor xyz,
+                                        c10::optional<torch::Tensor> mask,
+                                        double inv, double r2, int64_t k,
+                                        int64_t min_neighbors,
+                                        double std_ratio) {
+  check_f32(xyz, "xyz");
+  TORCH_CHECK(xyz.dim() == 3 && xyz.size(2) == 3, "xyz must be (B,N,3)");
+  const int64_t B = xyz.size(0), N = xyz.size(1);
+  TORCH_CHECK(B >= 1 && B <= 65535 && N >= 1, "noise_filter requires 1 <= B <= 65535, N >= 1");
+  TORCH_CHECK(N < (1L << 27), "noise_filter requires N < 2^27");
+  TORCH_CHECK(k >= 0 && k <= 16, "noise_filter requires 0 <= k <= 16");
+  TORCH_CHECK(min_neighbors >= 0, "noise_filter requires min_neighbors >= 0");
+  TORCH_CHECK(inv > 0.0 && std::isfinite(inv) && r2 >= 0.0, "noise_filter requires a finite 1 / radius > 0");
+  TORCH_CHECK(std_ratio >= 0.0, "noise_filter requires std_ratio >= 0");
+  const unsigned char* mp = nullptr;
+  if (mask.has_value()) {
+    const torch::Tensor& q = *mask;
+    TORCH_CHECK(q.is_cuda() && q.is_contiguous() &&
+                    q.scalar_type() == torch::kBool && q.dim() == 2 &&
+                    q.size(0) == B && q.size(1) == N &&
+                    q.device() == xyz.device(),
+                "mask must be contiguous bool (B,N) on the device of xyz");
+    mp = reinterpret_cast<const unsigned char*>(q.data_ptr<bool>());
+  }
+  int64_t T = 2;  // slots per cloud: a power of two >= 2 N
+  while (T < 2 * N) T <<= 1;
+  const int64_t blk = noise_filter_block();
+  const int64_t nblk = (N + blk - 1) / blk, nrun = (T + blk - 1) / blk;
+  auto iopt = xyz.options().dtype(torch::kInt32);
+  auto bopt = xyz.options().dtype(torch::kBool);
+  auto dopt = xyz.options().dtype(torch::kFloat64);
+  auto keys = torch::empty({B, T}, xyz.options().dtype(torch::kInt64));
+  auto cells = torch::empty({2, B, T}, iopt);
+  auto slot = torch::empty({B, N}, iopt);
+  auto sorted = torch::empty({B, N, 4}, xyz.options());
+  auto bsum = torch::empty({B, nrun}, iopt);
+  auto meta = torch::empty({2, B}, iopt);
+  auto part = torch::empty({B, 3, nblk}, dopt);
+  auto keep = torch::empty({B, N}, bopt);
+  auto count = torch::empty({B, N}, iopt);
+  auto md = torch::empty({B, N}, xyz.options());
+  auto stats = torch::empty({B, 3}, dopt);
+  auto ok = torch::empty({B}, bopt);
+  launch_noise_filter(
+      xyz.data_ptr<float>(), mp,
+      reinterpret_cast<unsigned long long*>(keys.data_ptr<int64_t>()),
+      cells.data_ptr<int>(), slot.data_ptr<int>(), sorted.data_ptr<float>(),
+      bsum.data_ptr<int>(), meta.data_ptr<int>(), part.data_ptr<double>(),
+      reinterpret_cast<unsigned char*>(keep.data_ptr<bool>()),
+      count.data_ptr<int>(), md.data_ptr<float>(), stats.data_ptr<double>(),
+      reinterpret_cast<unsigned char*>(ok.data_ptr<bool>()), (int)B, (int)N,
+      (int)T, (float)inv, (float)r2, (int)k,
+      (int)std::min<int64_t>(min_neighbors, INT32_MAX), std_ratio, stream());
+  return {keep, count, md, stats, ok};
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  m.def("noise_filter", &noise_filter);
+  m.attr("NOISE_FILTER_BLOCK") = noise_filter_block();
+  m.attr("NOISE_FILTER_SCAN") = noise_filter_scan();
   m.def("voxel_sample", &voxel_sample);
   m.attr("VOXEL_SAMPLE_BLOCK") = voxel_sample_block();
   m.attr("VOXEL_SAMPLE_SCAN") = voxel_sample_scan();

@@ -17,8 +17,14 @@ from .batch import Batch
 
 class SyntheticSceneFlow(SceneFlowDataset):
     def __init__(self, nb_points: int, length: int = 256, seed: int = 0, extent: float = 10.0,
-                 full_points=None, ground_fraction: float = 0.0):
+                 full_points=None, ground_fraction: float = 0.0, noise_fraction: float = 0.0):
         super().__init__(nb_points)
+        if not 0.0 <= float(noise_fraction) < 1.0:
+            raise ValueError(f"noise_fraction must be in [0, 1), got {noise_fraction}")
+        # share of the points replaced in both clouds by points uniform in
+        # the scene's bounding volume, with zero-flow ground truth that is
+        # masked out; 0 keeps the historical stream
+        self.noise_fraction = float(noise_fraction)
         if not 0.0 <= float(ground_fraction) < 1.0:
             raise ValueError(f"ground_fraction must be in [0, 1), got {ground_fraction}")
         # share of the points that lies on the plane y = -1.4 (2 cm noise)
@@ -51,6 +57,16 @@ class SyntheticSceneFlow(SceneFlowDataset):
             pc1[sel, 1] = (-1.4 + rng.normal(0.0, 0.02, size=k)).astype(np.float32)
         pc2 = pc1 @ rot.T + t + noise
         ground_truth = [np.ones_like(pc1[:, 0:1]), pc2 - pc1]
+        if self.noise_fraction > 0:
+            # drawn after everything above: the default stream is untouched
+            k = int(round(self.noise_fraction * n))
+            sel = rng.permutation(n)[:k]
+            lo = np.minimum(pc1.min(0), pc2.min(0))
+            hi = np.maximum(pc1.max(0), pc2.max(0))
+            pc1[sel] = (lo + rng.random((k, 3)) * (hi - lo)).astype(np.float32)
+            pc2[sel] = (lo + rng.random((k, 3)) * (hi - lo)).astype(np.float32)
+            ground_truth[0][sel] = 0.0
+            ground_truth[1][sel] = 0.0
         return [pc1, pc2], ground_truth
 
 

@@ -55,6 +55,18 @@ grid level with at most max_points occupied cells in pc1, every cell of which
 holds a sample; ``levels`` when there is none), and sample_cut_radius, the mean
 of sqrt(3) * voxel * 2**l*.  SYNTH builds its clouds with 4 * max_points
 points, as under --dense.  Without the flag nothing changes.
+
+--noise_filter (beyond the reference too) keeps isolated points out of the
+voxel sample: both full clouds get ops.noise_filter (--noise_radius,
+--noise_min_neighbors, --noise_k, --noise_std_ratio) and its keep mask goes
+into ops.voxel_sample as ``mask``.  It needs the full clouds, so it requires
+--sample voxel and raises ValueError otherwise.  It reports noise_ratio (share
+of pc1's points that are not kept), noise_sparse_ratio (share with fewer than
+min_neighbors neighbours), noise_far_ratio (share whose mean distance to the k
+nearest is above the threshold, or that have fewer than k neighbours) and
+noise_mean_dist (the filter's ``mean`` of pc1), averaged over the set;
+--dump_results also writes noise_mask.npy (~keep of the full pc1).  SYNTH
+replaces 2 % of its points by uniform noise when the flag is on.
 """
 
 from __future__ import annotations
@@ -92,7 +104,8 @@ def build_eval_dataset(args):
         full = 4 * args.max_points if getattr(args, "dense", False) or voxel else None
         return SyntheticSceneFlow(args.max_points, length=getattr(args, "synth_len", 32), seed=7,
                                   full_points=full,
-                                  ground_fraction=0.3 if getattr(args, "ground_fit", False) else 0.0)
+                                  ground_fraction=0.3 if getattr(args, "ground_fit", False) else 0.0,
+                                  noise_fraction=0.02 if getattr(args, "noise_filter", False) else 0.0)
     raise ValueError(f"Unknown dataset {args.dataset!r}")
 
 
@@ -132,6 +145,15 @@ def evaluate(args):
         levels=int(getattr(args, "sample_levels", 10)),
         seed=int(getattr(args, "sample_seed", 0)),
     )
+    denoise = bool(getattr(args, "noise_filter", False))
+    if denoise and not voxel:
+        raise ValueError("--noise_filter filters the full clouds: it requires --sample voxel")
+    noise_kw = dict(
+        radius=float(getattr(args, "noise_radius", 0.5)),
+        min_neighbors=int(getattr(args, "noise_min_neighbors", 4)),
+        k=int(getattr(args, "noise_k", 8)),
+        std_ratio=float(getattr(args, "noise_std_ratio", 2.0)),
+    )
     if dense or ego or obj or ground or voxel:
         from pvraft_amd import ops
     if dense or voxel:
@@ -170,6 +192,7 @@ def evaluate(args):
     obj_sums = [0.0] * 6
     ground_sums = [0.0] * 9
     sample_sums = [0.0] * 2
+    noise_sums = [0.0] * 4
     n_ng = 0
     n = 0
     for batch in loader:
@@ -181,8 +204,21 @@ def evaluate(args):
             # run without the flag makes, and the datasets stay untouched
             pc1_all, mask_all, flow_all = batch["full"]
             pc2_all = batch["full2"][0]
-            vs1 = ops.voxel_sample(pc1_all, args.max_points, **sample_kw)
-            vs2 = ops.voxel_sample(pc2_all, args.max_points, **sample_kw)
+            keep1 = keep2 = None
+            if denoise:
+                nf1 = ops.noise_filter(pc1_all, **noise_kw)
+                nf2 = ops.noise_filter(pc2_all, **noise_kw)
+                keep1, keep2 = nf1.keep, nf2.keep
+                el = nf1.count >= 0
+                far = el & (nf1.count < noise_kw["k"])
+                if noise_kw["k"] >= 1:
+                    far = far | (el & (nf1.mean_dist.double() > nf1.threshold.unsqueeze(1)))
+                noise_sums[0] += (~keep1).float().mean().item()
+                noise_sums[1] += (el & (nf1.count < noise_kw["min_neighbors"])).float().mean().item()
+                noise_sums[2] += far.float().mean().item()
+                noise_sums[3] += nf1.mean.mean().item()
+            vs1 = ops.voxel_sample(pc1_all, args.max_points, mask=keep1, **sample_kw)
+            vs2 = ops.voxel_sample(pc2_all, args.max_points, mask=keep2, **sample_kw)
             for name, vs in (("pc1", vs1), ("pc2", vs2)):
                 if int(vs.count[0]) < args.max_points:
                     raise ValueError(
@@ -279,6 +315,8 @@ def evaluate(args):
             np.save(os.path.join(d, "flow.npy"), final.cpu().numpy())
             if voxel:
                 np.save(os.path.join(d, "sample_idx1.npy"), sample_idx1.cpu().numpy())
+            if denoise:
+                np.save(os.path.join(d, "noise_mask.npy"), (~keep1[0]).cpu().numpy())
             if dense:
                 np.save(os.path.join(d, "pc1_full.npy"), pc1_full.cpu().numpy())
                 np.save(os.path.join(d, "flow_dense.npy"), flow_dense.cpu().numpy())
@@ -382,4 +420,13 @@ def evaluate(args):
             f"seed={sample_kw['seed']}] cut_level={smeans[0]:.3f} cut_radius={smeans[1]:.4f}"
         )
         results.update(sample_cut_level=smeans[0], sample_cut_radius=smeans[1])
+    if denoise:
+        nmeans = [v / max(n, 1) for v in noise_sums]
+        log.info(
+            f"[test {args.dataset} noise radius={noise_kw['radius']} min_neighbors={noise_kw['min_neighbors']} "
+            f"k={noise_kw['k']} std_ratio={noise_kw['std_ratio']}] ratio={nmeans[0]:.4f} "
+            f"sparse={nmeans[1]:.4f} far={nmeans[2]:.4f} mean_dist={nmeans[3]:.4f}"
+        )
+        results.update(noise_ratio=nmeans[0], noise_sparse_ratio=nmeans[1], noise_far_ratio=nmeans[2],
+                       noise_mean_dist=nmeans[3])
     return results

@@ -12,6 +12,8 @@ launch-collapse as the training step, applied to serving.
     dense = pred.predict_dense(pc1_full, pc2_full, k=3)   # (n1, 3)
     # ... of raw scans that still contain the ground:
     dense = pred.predict_dense(pc1_full, pc2_full, remove_ground=True)
+    # ... that also contain isolated noise points:
+    dense = pred.predict_dense(pc1_full, pc2_full, sampling="voxel", remove_noise=True)
 
     # flow plus the ego-motion it implies and a static/dynamic split:
     flow, ego = pred.predict_ego_motion(xyz1, xyz2)       # ego.R, ego.t, ...
@@ -123,7 +125,8 @@ class Predictor:
                       generator: Optional[torch.Generator] = None,
                       return_sparse: bool = False, remove_ground: bool = False,
                       ground_kw: Optional[dict] = None, sampling: str = "random",
-                      sample_kw: Optional[dict] = None):
+                      sample_kw: Optional[dict] = None, remove_noise: bool = False,
+                      noise_kw: Optional[dict] = None):
         """Flow for EVERY point of ``pc1_full`` ((n1,3) or (1,n1,3)).
 
         Draws ``points`` indices without replacement from each full cloud
@@ -159,6 +162,19 @@ class Predictor:
         the ValueError for a cloud with fewer than ``points`` usable points
         is the one host synchronisation per cloud.  Any other ``sampling``
         than "random" or "voxel" raises ValueError.
+
+        ``remove_noise=True`` keeps isolated points (flying pixels, returns
+        from rain or dust) out of the samples: each full cloud gets its own
+        ``ops.noise_filter(cloud, **noise_kw)`` on the WHOLE cloud (with
+        ``remove_ground`` the ground is not masked out first: points just
+        above it would lose their neighbours) and the usable points are
+        ``keep``, and additionally ``~ground`` with ``remove_ground``.  With
+        ``sampling="voxel"`` that goes in as the sampler's mask, with
+        "random" it takes the compaction path of ``remove_ground``; the count
+        checks, their messages and the one host synchronisation per cloud are
+        the same.  The dense flow still covers every point, and with
+        ``return_sparse`` the tuple gains a LAST entry, the (n1,) bool noise
+        mask ``~keep`` of ``pc1_full``.
         """
         from pvraft_amd import ops
 
@@ -181,14 +197,21 @@ class Predictor:
         gdev = generator.device if generator is not None else torch.device("cpu")
         subs, idxs = [], []
         ground1 = None
+        noise1 = None
         for name, pc in zip(("pc1_full", "pc2_full"), clouds):
+            usable_mask = None  # (1, n) bool, None: every point
             if remove_ground:
                 fit = ops.fit_plane(pc.float().unsqueeze(0), **(ground_kw or {}))
                 if ground1 is None:
                     ground1 = fit.ground[0]
+                usable_mask = ~fit.ground
+            if remove_noise:
+                nf = ops.noise_filter(pc.float().unsqueeze(0), **(noise_kw or {}))
+                if noise1 is None:
+                    noise1 = ~nf.keep[0]
+                usable_mask = nf.keep if usable_mask is None else usable_mask & nf.keep
             if sampling == "voxel":
-                vs = ops.voxel_sample(pc.float().unsqueeze(0), points,
-                                      mask=~fit.ground if remove_ground else None, **(sample_kw or {}))
+                vs = ops.voxel_sample(pc.float().unsqueeze(0), points, mask=usable_mask, **(sample_kw or {}))
                 usable = int(vs.count[0])  # host sync: the count
                 if usable < points:
                     raise ValueError(
@@ -196,11 +219,12 @@ class Predictor:
                         "the predictor samples"
                     )
                 idx = vs.idx[0]
-            elif remove_ground:
-                keep = (~fit.ground[0]).nonzero().squeeze(1)  # host sync: the count
+            elif usable_mask is not None:
+                keep = usable_mask[0].nonzero().squeeze(1)  # host sync: the count
                 if keep.numel() < points:
+                    what = "non-ground" if not remove_noise else ("usable" if remove_ground else "non-noise")
                     raise ValueError(
-                        f"{name} has {keep.numel()} non-ground points, fewer than the {points} the predictor samples"
+                        f"{name} has {keep.numel()} {what} points, fewer than the {points} the predictor samples"
                     )
                 sel = torch.randperm(keep.numel(), generator=generator, device=gdev)[:points].to(self.device)
                 idx = keep[sel]
@@ -212,7 +236,10 @@ class Predictor:
         dense, _, _ = ops.knn_interpolate(subs[0], flow_sub, clouds[0].float().unsqueeze(0), k)
         dense = dense[0].to(pc1_full.dtype)
         if return_sparse:
+            out = (dense, idxs[0], flow_sub[0])
             if remove_ground:
-                return dense, idxs[0], flow_sub[0], ground1
-            return dense, idxs[0], flow_sub[0]
+                out = out + (ground1,)
+            if remove_noise:
+                out = out + (noise1,)
+            return out
         return dense

@@ -1506,3 +1506,96 @@ def voxel_sample(
     if _use_hip(xyz) and B > 0 and N > 0:
         return VoxelSample(*_EXT.voxel_sample(xyz, mask, m, inv, levels, seed))
     return VoxelSample(*reference.voxel_sample(xyz, m, inv, levels, mask, seed))
+
+
+# ---------------------------------------------------------------------------
+# noise filter (csrc/noise_filter.hip)
+# ---------------------------------------------------------------------------
+
+
+class NoiseFilter(NamedTuple):
+    """Result of ``noise_filter``: keep (B,N) bool, eligible and neither sparse
+    nor far; count (B,N) int32 neighbours within the radius, -1 for an
+    ineligible point (all -1 if a kernel cap was hit); mean_dist (B,N) fp32
+    mean distance to the k nearest neighbours, +INF if count < k, k == 0 or the
+    point is ineligible; mean, std, threshold (B,) float64 statistics of the
+    finite mean_dist; ok (B,) bool, False only if a capped loop hit its cap
+    (then keep is all False and count all -1)."""
+
+    keep: Tensor
+    count: Tensor
+    mean_dist: Tensor
+    mean: Tensor
+    std: Tensor
+    threshold: Tensor
+    ok: Tensor
+
+
+def noise_filter(
+    xyz: Tensor, radius: float = 0.5, min_neighbors: int = 4, k: int = 8, std_ratio: float = 2.0,
+    mask: Optional[Tensor] = None,
+) -> NoiseFilter:
+    """Flags isolated points of a cloud by two neighbour statistics: xyz
+    (B,N,3), optional mask (B,N) bool -> ``NoiseFilter``.  radius > 0,
+    min_neighbors >= 0, 0 <= k <= 16, std_ratio >= 0, N < 2**27; anything else
+    raises ValueError.  The same ``count`` and ``mean_dist`` bits on every
+    backend and in every run.
+
+    Cells.  ``inv = fp32(1) / fp32(radius)`` is computed on the host; per
+    coordinate ``q = floor(fp32(x * inv))``.  A point is eligible iff it is
+    masked, its three coordinates are finite and -2**20 <= q < 2**20 for all
+    three; its cell is ``c = int(q)``: the level-0 rules of ``voxel_sample``.
+    A product ``x * inv`` that is a denormal fp32 number is unspecified.
+
+    Neighbour.  j is a neighbour of i iff j != i, both are eligible points of
+    the same cloud, ``max|c_i - c_j| <= 1`` and ``d2 <= r2`` with ``r2 =
+    fp32(radius) * fp32(radius)`` rounded once and ``d2 = (dx*dx + dy*dy) +
+    dz*dz``, ``dx = x_i - x_j``, every operation an fp32 operation rounded on
+    its own.  The cell condition is part of the definition: two points within
+    a rounding error of ``radius`` can land two cells apart, and making the
+    27-cell stencil the rule keeps every backend on the same integers.  The
+    relation is symmetric.
+
+    ``count_i`` is the number of neighbours; i is sparse iff ``count_i <
+    min_neighbors``.  For k >= 1 and ``count_i >= k``, ``mean_dist_i`` takes
+    the k smallest d2 among the neighbours (a multiset), ascending, their
+    correctly rounded fp32 square roots summed left to right in fp32, divided
+    by fp32(k); it does not depend on the order the neighbours are visited.
+
+    Statistics over S, the points with finite mean_dist, in float64: ``mean``,
+    the population ``std = sqrt(mean((m - mean)**2))`` in two passes, and
+    ``threshold = mean + std_ratio * std``; all 0.0 when S is empty or k == 0.
+    i is far iff k >= 1 and (``count_i < k`` or ``float64(mean_dist_i) >
+    threshold``), against the threshold this call returns.  ``keep_i =
+    eligible_i and not sparse_i and not far_i``.
+
+    GPU: csrc/noise_filter.hip: a hashed cell grid with edge ``radius`` built
+    with integer atomics, a counting sort of the points by cell, one lane per
+    point over its 27 cells with the k smallest d2 in registers, fixed-order
+    float64 folds; 9 launches, no (N,N) tensor, no host synchronisation,
+    bit-reproducible and equivariant under a permutation of the points.  All
+    points in one cell cost O(N**2) tests.  Every probe loop is capped at the
+    table size; should a cap ever be hit, that cloud comes back with ok =
+    False, keep all False and count all -1.  Not differentiable.
+    bf16/fp16/fp64 or non-contiguous inputs are converted to contiguous fp32
+    here.
+
+    The defaults (0.5 m, 4 neighbours, k = 8, 2 sigma) are untuned guesses at
+    metric driving scenes: nobody has tuned them on real data.
+    """
+    inv, r2, min_neighbors, k, std_ratio = reference.noise_params(radius, min_neighbors, k, std_ratio)
+    if xyz.dim() != 3 or xyz.shape[-1] != 3:
+        raise ValueError(f"noise_filter needs xyz (B,N,3), got {tuple(xyz.shape)}")
+    B, N = xyz.shape[:2]
+    if not N < (1 << 27):
+        raise ValueError(f"noise_filter requires N < 2**27, got {N}")
+    if mask is not None:
+        if mask.shape != xyz.shape[:2]:
+            raise ValueError(f"noise_filter needs mask (B,N), got {tuple(mask.shape)}")
+        mask = mask.detach().bool().contiguous()
+    xyz = xyz.detach().float().contiguous()
+    if _use_hip(xyz) and B > 0 and N > 0:
+        keep, count, md, stats, ok = _EXT.noise_filter(xyz, mask, inv, r2, k, min_neighbors, std_ratio)
+    else:
+        keep, count, md, stats, ok = reference.noise_filter(xyz, inv, r2, min_neighbors, k, std_ratio, mask)
+    return NoiseFilter(keep, count, md, stats[:, 0], stats[:, 1], stats[:, 2], ok)

@@ -728,6 +728,18 @@ def voxel_params(m, voxel, levels, seed):
     return m, inv, levels, seed & 0xFFFFFFFF
 
 
+def grid_cells(x: Tensor, inv: float, mask: Optional[Tensor]):
+    """Level-0 cell rules shared by ``voxel_sample`` and ``noise_filter``: x
+    (...,3) fp32 -> eligible (...) bool and ``q = floor(fp32(x * inv))``
+    (...,3) fp32.  Eligible: masked, finite, -2**20 <= q < 2**20 on all three
+    axes; the cell of an eligible point is ``int(q)``."""
+    q = torch.floor(x * torch.tensor(inv, dtype=torch.float32, device=x.device))
+    el = torch.isfinite(x).all(-1) & (q >= -VOXEL_RANGE).all(-1) & (q < VOXEL_RANGE).all(-1)
+    if mask is not None:
+        el = el & mask
+    return el, q
+
+
 def voxel_sample(xyz: Tensor, m: int, inv: float, levels: int, mask: Optional[Tensor], seed: int):
     """Torch version of ``ops.voxel_sample`` with the prepared numbers of
     ``voxel_params``: one stable sort by the hash puts the points in tag
@@ -745,11 +757,7 @@ def voxel_sample(xyz: Tensor, m: int, inv: float, levels: int, mask: Optional[Te
             return (torch.full((B, m), -1, **i64), torch.zeros(B, dtype=torch.int32, device=dev),
                     torch.zeros(B, 0, dtype=torch.int32, device=dev),
                     torch.zeros(B, L, dtype=torch.int32, device=dev))
-        x = xyz.float()
-        q = torch.floor(x * torch.tensor(inv, dtype=torch.float32, device=dev))
-        el = torch.isfinite(x).all(-1) & (q >= -VOXEL_RANGE).all(-1) & (q < VOXEL_RANGE).all(-1)
-        if mask is not None:
-            el = el & mask
+        el, q = grid_cells(xyz.float(), inv, mask)
         f = torch.where(el.unsqueeze(-1), q, torch.zeros_like(q)).long() + VOXEL_RANGE  # biased fields, 21 bits
         ar = torch.arange(N, **i64)
         b = torch.arange(B, **i64)
@@ -783,3 +791,105 @@ def voxel_sample(xyz: Tensor, m: int, inv: float, levels: int, mask: Optional[Te
         idx = torch.full((B, m), -1, **i64)
         idx[:, :mm] = out[:, :mm]
         return idx, take.int(), rank.int(), occupied.int()
+
+
+# ---------------------------------------------------------------------------
+# Noise filter (absent in the reference): radius count + k-nearest mean distance
+# ---------------------------------------------------------------------------
+
+NOISE_MAX_K = 16
+NOISE_PAIR_BUDGET = 1 << 22  # pair tests held in memory at once (chunk * N)
+
+
+def noise_params(radius, min_neighbors, k, std_ratio):
+    """Checks the scalar arguments of ``noise_filter`` and returns the numbers
+    every backend computes with: ``inv = fp32(1) / fp32(radius)`` and ``r2 =
+    fp32(radius) * fp32(radius)`` (rounded once) as Python floats,
+    min_neighbors, k and std_ratio.  Raises ValueError."""
+    try:
+        radius, min_neighbors, k, std_ratio = float(radius), int(min_neighbors), int(k), float(std_ratio)
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"noise_filter: bad argument: {e}") from None
+    if not (radius > 0 and math.isfinite(radius)):
+        raise ValueError(f"noise_filter requires a finite radius > 0, got {radius}")
+    if not min_neighbors >= 0:
+        raise ValueError(f"noise_filter requires min_neighbors >= 0, got {min_neighbors}")
+    if not 0 <= k <= NOISE_MAX_K:
+        raise ValueError(f"noise_filter requires 0 <= k <= {NOISE_MAX_K}, got {k}")
+    if not (std_ratio >= 0 and math.isfinite(std_ratio)):
+        raise ValueError(f"noise_filter requires a finite std_ratio >= 0, got {std_ratio}")
+    r32 = torch.tensor(radius, dtype=torch.float32)
+    inv = float((torch.ones((), dtype=torch.float32) / r32).item())
+    if not (r32.item() > 0 and inv > 0 and math.isfinite(inv)):
+        raise ValueError(f"noise_filter: 1 / radius is not a positive fp32 number for radius = {radius}")
+    return inv, float((r32 * r32).item()), min_neighbors, k, std_ratio
+
+
+def noise_filter(xyz: Tensor, inv: float, r2: float, min_neighbors: int, k: int, std_ratio: float,
+                 mask: Optional[Tensor]):
+    """Torch version of ``ops.noise_filter`` with the prepared numbers of
+    ``noise_params``: both neighbour conditions (cells at most one apart on
+    every axis, d2 <= r2) by brute force over chunks of rows, so no more than
+    chunk x N pair tests are in memory at once; the k smallest d2 by
+    ``topk``, their square roots summed left to right in fp32.  No host
+    synchronisation.  Returns keep (B,N) bool, count (B,N) int32, mean_dist
+    (B,N) fp32, stats (B,3) fp64 = mean, std, threshold, ok (B,) bool."""
+    with torch.no_grad():
+        B, N, _ = xyz.shape
+        dev = xyz.device
+        x = xyz.float()
+        inf = float("inf")
+        count = torch.full((B, N), -1, dtype=torch.int32, device=dev)
+        md = torch.full((B, N), inf, dtype=torch.float32, device=dev)
+        ok = torch.ones(B, dtype=torch.bool, device=dev)
+        if B == 0 or N == 0:
+            return (torch.zeros(B, N, dtype=torch.bool, device=dev), count, md,
+                    torch.zeros(B, 3, dtype=torch.float64, device=dev), ok)
+        el, q = grid_cells(x, inv, mask)
+        c = torch.where(el.unsqueeze(-1), q, torch.zeros_like(q)).to(torch.int32)  # cells, exact
+        r2t = torch.tensor(r2, dtype=torch.float32, device=dev)
+        ar = torch.arange(N, device=dev)
+        chunk = max(1, min(N, NOISE_PAIR_BUDGET // N))
+        for b in range(B):
+            xb, cb, eb = x[b], c[b], el[b]
+            for s in range(0, N, chunk):
+                e = min(N, s + chunk)
+                nb = eb[s:e, None] & eb[None, :] & (ar[s:e, None] != ar[None, :])
+                d2 = None
+                for a in range(3):
+                    nb &= (cb[s:e, None, a] - cb[None, :, a]).abs() <= 1
+                    d = xb[s:e, None, a] - xb[None, :, a]
+                    d = d * d
+                    d2 = d if d2 is None else d2 + d  # (dx*dx + dy*dy) + dz*dz, each op rounded
+                nb &= d2 <= r2t
+                n = nb.sum(1)
+                count[b, s:e] = torch.where(eb[s:e], n, torch.full_like(n, -1)).int()
+                if k >= 1:
+                    d2 = torch.where(nb, d2, torch.full_like(d2, inf))
+                    if N < k:
+                        d2 = torch.cat([d2, d2.new_full((e - s, k - N), inf)], 1)
+                    small = torch.topk(d2, k, dim=1, largest=False, sorted=True).values
+                    # torch's vectorised fp32 sqrt is not correctly rounded on every
+                    # backend; the fp64 root rounded to fp32 is (53 >= 2 * 24 + 2)
+                    root = torch.sqrt(small.double()).float()
+                    tot = root[:, 0]
+                    for j in range(1, k):
+                        tot = tot + root[:, j]
+                    m = tot / torch.tensor(float(k), dtype=torch.float32, device=dev)
+                    md[b, s:e] = torch.where(eb[s:e] & (n >= k), m, torch.full_like(m, inf))
+        stats = torch.zeros(B, 3, dtype=torch.float64, device=dev)
+        far = torch.zeros_like(el)
+        if k >= 1:
+            fin = torch.isfinite(md)
+            m64 = torch.where(fin, md.double(), torch.zeros((), dtype=torch.float64, device=dev))
+            cnt = fin.sum(1).double()
+            some = cnt > 0
+            div = cnt.clamp_min(1.0)
+            mean = torch.where(some, m64.sum(1) / div, torch.zeros_like(div))
+            dev2 = torch.where(fin, (m64 - mean.unsqueeze(1)) ** 2, torch.zeros_like(m64))
+            std = torch.where(some, torch.sqrt(dev2.sum(1) / div), torch.zeros_like(div))
+            thr = mean + std_ratio * std
+            stats = torch.stack([mean, std, thr], 1)
+            far = (count < k) | (md.double() > thr.unsqueeze(1))
+        keep = el & (count >= min_neighbors) & ~far
+        return keep, count, md, stats, ok

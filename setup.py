@@ -41,6 +41,7 @@ SOURCES = [
     "pvraft_amd/csrc/cluster.hip",
     "pvraft_amd/csrc/plane_fit.hip",
     "pvraft_amd/csrc/voxel_sample.hip",
+    "pvraft_amd/csrc/noise_filter.hip",
 ]
 
 setup(

@@ -39,6 +39,11 @@ def parse_args():
     parser.add_argument("--sample_voxel", help="finest cell edge of the voxel sampler (m)", default=0.1, type=float)
     parser.add_argument("--sample_levels", help="nested grid levels of the voxel sampler", default=10, type=int)
     parser.add_argument("--sample_seed", help="seed of the voxel sampler's tie-breaking hash", default=0, type=int)
+    parser.add_argument("--noise_filter", help="with --sample voxel: filter both full clouds with ops.noise_filter, keep isolated points out of the sample and report noise_* metrics", action="store_true")
+    parser.add_argument("--noise_radius", help="neighbour radius of the noise filter (m)", default=0.5, type=float)
+    parser.add_argument("--noise_min_neighbors", help="a point with fewer neighbours within the radius is noise", default=4, type=int)
+    parser.add_argument("--noise_k", help="nearest neighbours in the mean-distance statistic of the noise filter (0 disables it)", default=8, type=int)
+    parser.add_argument("--noise_std_ratio", help="a point whose mean distance exceeds mean + ratio * std is noise", default=2.0, type=float)
     return parser.parse_args()
 
 
