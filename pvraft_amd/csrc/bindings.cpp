@@ -64,6 +64,19 @@ void launch_noise_filter(const float*, const unsigned char*, unsigned long long*
                          float, float, int, int, double, hipStream_t);
 int noise_filter_block();
 int noise_filter_scan();
+void launch_grid_nn_build(const float*, const unsigned char*, unsigned long long*,
+                          int*, int*, float*, int*, int*, long, unsigned char*,
+                          float*, float*, const float*, const float*, int, int,
+                          int, float, hipStream_t);
+void launch_grid_nn_query(const float*, const unsigned char*, const float*,
+                          const float*, const unsigned long long*, const int*,
+                          const float*, const int*, const int*, unsigned char*,
+                          int*, float*, float*, float*, int*, int, int, int, int,
+                          float, float, float, hipStream_t);
+void launch_icp_commit(const int*, const unsigned char*, const float*,
+                       const float*, float*, float*, int*, int*, unsigned char*,
+                       int, hipStream_t);
+int grid_nn_block();
 void launch_morton_keys(const float*, const float*, const float*, long*,
                         int, long, hipStream_t);
 void launch_gather_edge_fwd(const void*, const int*, const float*, void*,
@@ -1943,7 +1956,178 @@ std::vector<torch::Tensor> noise_filter(torch::Tensor xyz,
   return {keep, count, md, stats, ok};
 }
 
+// Grid search and ICP (csrc/grid_nn.hip).
+namespace {
+
+const unsigned char* gn_mask(const c10::optional<torch::Tensor>& mask,
+                             const torch::Tensor& like, const char* name) {
+  if (!mask.has_value()) return nullptr;
+  const torch::Tensor& q = *mask;
+  TORCH_CHECK(q.is_cuda() && q.is_contiguous() &&
+                  q.scalar_type() == torch::kBool && q.dim() == 2 &&
+                  q.size(0) == like.size(0) && q.size(1) == like.size(1) &&
+                  q.device() == like.device(),
+              name, " must be contiguous bool (B,N) on the device of its cloud");
+  return reinterpret_cast<const unsigned char*>(q.data_ptr<bool>());
+}
+
+const float* gn_pose(const c10::optional<torch::Tensor>& v,
+                     const torch::Tensor& like, bool rot, const char* name) {
+  if (!v.has_value()) return nullptr;
+  const torch::Tensor& q = *v;
+  check_f32(q, name);
+  TORCH_CHECK(q.device() == like.device() && q.size(0) == like.size(0) &&
+                  (rot ? (q.dim() == 3 && q.size(1) == 3 && q.size(2) == 3)
+                       : (q.dim() == 2 && q.size(1) == 3)),
+              name, rot ? " must be (B,3,3)" : " must be (B,3)",
+              " on the device of the query");
+  return q.data_ptr<float>();
+}
+
+// The workspaces of one grid over `support`: torch allocations of the call;
+// every word is written before it is read.
+struct GridNN {
+  torch::Tensor keys, cells, slot, sorted, bsum;
+  int64_t T;
+  GridNN(const torch::Tensor& support) {
+    const int64_t B = support.size(0), M = support.size(1);
+    T = 2;  // slots per cloud: a power of two >= 2 M
+    while (T < 2 * M) T <<= 1;
+    const int64_t blk = grid_nn_block(), nrun = (T + blk - 1) / blk;
+    auto iopt = support.options().dtype(torch::kInt32);
+    keys = torch::empty({B, T}, support.options().dtype(torch::kInt64));
+    cells = torch::empty({2, B, T}, iopt);
+    slot = torch::empty({B, M}, iopt);
+    sorted = torch::empty({B, M, 4}, support.options());
+    bsum = torch::empty({B, nrun}, iopt);
+  }
+  unsigned long long* k() {
+    return reinterpret_cast<unsigned long long*>(keys.data_ptr<int64_t>());
+  }
+};
+
+void gn_check(const torch::Tensor& query, const torch::Tensor& support,
+              double inv, double r2, const char* op) {
+  check_f32(query, "query");
+  check_f32(support, "support");
+  TORCH_CHECK(query.dim() == 3 && query.size(2) == 3, op, ": query must be (B,N,3)");
+  TORCH_CHECK(support.dim() == 3 && support.size(2) == 3 &&
+                  support.size(0) == query.size(0) &&
+                  support.device() == query.device(),
+              op, ": support must be (B,M,3) on the device of the query");
+  const int64_t B = query.size(0), Nq = query.size(1), M = support.size(1);
+  TORCH_CHECK(B >= 1 && B <= 65535 && Nq >= 1 && M >= 1, op,
+              " requires 1 <= B <= 65535 and at least one point per cloud");
+  TORCH_CHECK(Nq < (1L << 27) && M < (1L << 27), op, " requires N, M < 2^27");
+  TORCH_CHECK(inv > 0.0 && std::isfinite(inv) && r2 >= 0.0, op,
+              " requires a finite 1 / radius > 0");
+}
+
+}  // namespace
+
+// query (B,Nq,3), support (B,M,3) f32, optional masks, optional R (B,3,3) and
+// t (B,3) read on the device, inv = fp32(1 / radius) and r2 = fp32(radius)^2
+// from the caller -> {idx (B,Nq) i32, d2 (B,Nq) f32, ok (B) bool}.  6 launches,
+// no host synchronisation.
+std::vector<torch::Tensor> nearest_in_radius(
+    torch::Tensor query, torch::Tensor support,
+    c10::optional<torch::Tensor> query_mask,
+    c10::optional<torch::Tensor> support_mask, c10::optional<torch::Tensor> R,
+    c10::optional<torch::Tensor> t, double inv, double r2) {
+  gn_check(query, support, inv, r2, "nearest_in_radius");
+  TORCH_CHECK(R.has_value() == t.has_value(), "nearest_in_radius: R and t go together");
+  const int64_t B = query.size(0), Nq = query.size(1), M = support.size(1);
+  const unsigned char* qm = gn_mask(query_mask, query, "query_mask");
+  const unsigned char* sm = gn_mask(support_mask, support, "support_mask");
+  const float* Rp = gn_pose(R, query, true, "R");
+  const float* tp = gn_pose(t, query, false, "t");
+  GridNN g(support);
+  auto iopt = query.options().dtype(torch::kInt32);
+  auto status = torch::empty({B}, iopt);
+  auto idx = torch::empty({B, Nq}, iopt);
+  auto d2 = torch::empty({B, Nq}, query.options());
+  auto ok = torch::empty({B}, query.options().dtype(torch::kBool));
+  unsigned char* okp = reinterpret_cast<unsigned char*>(ok.data_ptr<bool>());
+  launch_grid_nn_build(support.data_ptr<float>(), sm, g.k(), g.cells.data_ptr<int>(),
+                       g.slot.data_ptr<int>(), g.sorted.data_ptr<float>(),
+                       g.bsum.data_ptr<int>(), status.data_ptr<int>(), B, okp,
+                       nullptr, nullptr, nullptr, nullptr, (int)B, (int)M,
+                       (int)g.T, (float)inv, stream());
+  launch_grid_nn_query(query.data_ptr<float>(), qm, Rp, tp, g.k(),
+                       g.cells.data_ptr<int>(), g.sorted.data_ptr<float>(),
+                       g.bsum.data_ptr<int>(), status.data_ptr<int>(), okp,
+                       idx.data_ptr<int>(), d2.data_ptr<float>(), nullptr, nullptr,
+                       nullptr, (int)B, (int)Nq, (int)M, (int)g.T, (float)inv,
+                       (float)r2, 1.0f, stream());
+  return {idx, d2, ok};
+}
+
+// Point-to-point ICP of src (B,N,3) against dst (B,M,3): the grid over dst
+// once, then per round search / rigid_fit (iters = 0) / commit, and a closing
+// search: 5 + 3 * iters + 1 launches, no host synchronisation.  th2 =
+// fp32(thresh)^2 from the caller.  -> {R (B,3,3), t (B,3), idx (B,N) i32, d2
+// (B,N), matched (B) i32, rounds (B) i32, ok (B) bool}.
+std::vector<torch::Tensor> icp_refine(
+    torch::Tensor src, torch::Tensor dst, c10::optional<torch::Tensor> src_mask,
+    c10::optional<torch::Tensor> dst_mask, c10::optional<torch::Tensor> R0,
+    c10::optional<torch::Tensor> t0, double inv, double r2, double th2,
+    int64_t iters) {
+  gn_check(src, dst, inv, r2, "icp_refine");
+  TORCH_CHECK(iters >= 0 && iters <= 64, "icp_refine requires 0 <= iters <= 64");
+  TORCH_CHECK(th2 > 0.0 && std::isfinite(th2), "icp_refine requires a finite thresh^2 > 0");
+  const int64_t B = src.size(0), N = src.size(1), M = dst.size(1);
+  const unsigned char* sm = gn_mask(src_mask, src, "src_mask");
+  const unsigned char* dm = gn_mask(dst_mask, dst, "dst_mask");
+  const float* R0p = gn_pose(R0, src, true, "R0");
+  const float* t0p = gn_pose(t0, src, false, "t0");
+  GridNN g(dst);
+  auto iopt = src.options().dtype(torch::kInt32);
+  auto bopt = src.options().dtype(torch::kBool);
+  // rows: status, stopped, rounds, then one match counter per search
+  auto state = torch::empty({3 + iters + 1, B}, iopt);
+  int* st = state.data_ptr<int>();
+  auto R = torch::empty({B, 3, 3}, src.options());
+  auto t = torch::empty({B, 3}, src.options());
+  auto Rfit = torch::empty({B, 3, 3}, src.options());
+  auto tfit = torch::empty({B, 3}, src.options());
+  auto res = torch::empty({B, N}, src.options());
+  auto fit_ok = torch::empty({B}, bopt);
+  auto mdst = torch::empty({B, N, 3}, src.options());
+  auto wgt = torch::empty({B, N}, src.options());
+  auto idx = torch::empty({B, N}, iopt);
+  auto d2 = torch::empty({B, N}, src.options());
+  auto ok = torch::empty({B}, bopt);
+  unsigned char* okp = reinterpret_cast<unsigned char*>(ok.data_ptr<bool>());
+  unsigned char* fop = reinterpret_cast<unsigned char*>(fit_ok.data_ptr<bool>());
+  launch_grid_nn_build(dst.data_ptr<float>(), dm, g.k(), g.cells.data_ptr<int>(),
+                       g.slot.data_ptr<int>(), g.sorted.data_ptr<float>(),
+                       g.bsum.data_ptr<int>(), st, (3 + iters + 1) * B, okp,
+                       R.data_ptr<float>(), t.data_ptr<float>(), R0p, t0p, (int)B,
+                       (int)M, (int)g.T, (float)inv, stream());
+  for (int64_t k = 0; k <= iters; ++k) {
+    launch_grid_nn_query(src.data_ptr<float>(), sm, R.data_ptr<float>(),
+                         t.data_ptr<float>(), g.k(), g.cells.data_ptr<int>(),
+                         g.sorted.data_ptr<float>(), g.bsum.data_ptr<int>(), st, okp,
+                         idx.data_ptr<int>(), d2.data_ptr<float>(),
+                         mdst.data_ptr<float>(), wgt.data_ptr<float>(),
+                         st + (3 + k) * B, (int)B, (int)N, (int)M, (int)g.T,
+                         (float)inv, (float)r2, (float)th2, stream());
+    if (k == iters) break;
+    launch_rigid_fit(src.data_ptr<float>(), mdst.data_ptr<float>(),
+                     wgt.data_ptr<float>(), Rfit.data_ptr<float>(),
+                     tfit.data_ptr<float>(), res.data_ptr<float>(), fop, (int)B,
+                     (int)N, 1.0f, 0, stream());
+    launch_icp_commit(st + (3 + k) * B, fop, Rfit.data_ptr<float>(),
+                      tfit.data_ptr<float>(), R.data_ptr<float>(),
+                      t.data_ptr<float>(), st + B, st + 2 * B, okp, (int)B,
+                      stream());
+  }
+  return {R, t, idx, d2, state[3 + iters], state[2], ok};
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  m.def("nearest_in_radius", &nearest_in_radius);
+  m.def("icp_refine", &icp_refine);
   m.def("noise_filter", &noise_filter);
   m.attr("NOISE_FILTER_BLOCK") = noise_filter_block();
   m.attr("NOISE_FILTER_SCAN") = noise_filter_scan();

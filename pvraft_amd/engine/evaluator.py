@@ -67,6 +67,19 @@ nearest is above the threshold, or that have fewer than k neighbours) and
 noise_mean_dist (the filter's ``mean`` of pc1), averaged over the set;
 --dump_results also writes noise_mask.npy (~keep of the full pc1).  SYNTH
 replaces 2 % of its points by uniform noise when the flag is on.
+
+--ego_icp (beyond the reference too) refines the ego-motion fit by point-to-point
+ICP: the points the fit calls static are registered against the FULL second
+scan (the loader's "full2" cloud, which the network never sees whole) with
+ops.icp_refine started from the fitted motion (--icp_max_dist, --icp_thresh,
+--icp_iters).  It builds on the ego fit, so it requires --ego_motion and raises
+ValueError otherwise.  It reports icp_rot_err_deg and icp_trans_err (the
+formulas of the ego_* keys against the same ground-truth fit), icp_match_ratio
+(matched share of the static points), icp_rmse (root of the mean matched
+squared distance under the refined motion, a residual that needs no ground
+truth) and icprigid_* metrics of the flow whose static points are snapped onto
+the refined motion; --dump_results also writes icp_R.npy, icp_t.npy, icp_idx.npy
+and icp_d2.npy.  Without the flag nothing changes.
 """
 
 from __future__ import annotations
@@ -154,11 +167,19 @@ def evaluate(args):
         k=int(getattr(args, "noise_k", 8)),
         std_ratio=float(getattr(args, "noise_std_ratio", 2.0)),
     )
+    ego_icp = bool(getattr(args, "ego_icp", False))
+    if ego_icp and not ego:
+        raise ValueError("--ego_icp refines the ego-motion fit: it requires --ego_motion")
+    icp_kw = dict(
+        max_dist=float(getattr(args, "icp_max_dist", 1.0)),
+        thresh=float(getattr(args, "icp_thresh", 0.1)),
+        iters=int(getattr(args, "icp_iters", 10)),
+    )
     if dense or ego or obj or ground or voxel:
         from pvraft_amd import ops
     if dense or voxel:
         dataset.return_full = True
-    if voxel:
+    if voxel or ego_icp:
         dataset.return_full2 = True
     loader = DataLoader(
         dataset,
@@ -193,6 +214,7 @@ def evaluate(args):
     ground_sums = [0.0] * 9
     sample_sums = [0.0] * 2
     noise_sums = [0.0] * 4
+    icp_sums = [0.0] * 8
     n_ng = 0
     n = 0
     for batch in loader:
@@ -274,6 +296,23 @@ def evaluate(args):
             rigid_m = compute_epe(flow_rigid, batch)
             for j, v in enumerate((rot_err, trans_err, fit.static.float().mean().item()) + tuple(rigid_m)):
                 ego_sums[j] += v
+            if ego_icp:
+                icp = ops.icp_refine(pc1, batch["full2"][0].float(), R0=fit.R, t0=fit.t, src_mask=fit.static,
+                                     **icp_kw)
+                rel = icp.R @ gt_fit.R.transpose(1, 2)
+                cos = ((rel.diagonal(dim1=1, dim2=2).sum(-1) - 1) / 2).clamp(-1, 1)
+                icp_rot_err = torch.rad2deg(torch.acos(cos)).mean().item()
+                icp_trans_err = (icp.t - gt_fit.t).norm(dim=-1).mean().item()
+                found = icp.idx >= 0
+                n_static = fit.static.sum().item()
+                n_found = found.sum().item()
+                match_ratio = n_found / n_static if n_static else 0.0
+                rmse = (icp.d2[found].double().mean().sqrt().item()) if n_found else 0.0
+                icp_flow = pc1 @ icp.R.transpose(1, 2) + icp.t.unsqueeze(1) - pc1
+                flow_icprigid = torch.where(fit.static.unsqueeze(-1), icp_flow, final.float())
+                icprigid_m = compute_epe(flow_icprigid, batch)
+                for j, v in enumerate((icp_rot_err, icp_trans_err, match_ratio, rmse) + tuple(icprigid_m)):
+                    icp_sums[j] += v
         if obj:
             pc1 = batch["sequence"][0].float()
             om = ops.object_motion(pc1, final.float(), ego=fit if ego else None, ego_thresh=ego_thresh,
@@ -325,6 +364,11 @@ def evaluate(args):
                 np.save(os.path.join(d, "ego_t.npy"), fit.t.cpu().numpy())
                 np.save(os.path.join(d, "static_mask.npy"), fit.static.cpu().numpy())
                 np.save(os.path.join(d, "flow_rigid.npy"), flow_rigid.cpu().numpy())
+            if ego_icp:
+                np.save(os.path.join(d, "icp_R.npy"), icp.R.cpu().numpy())
+                np.save(os.path.join(d, "icp_t.npy"), icp.t.cpu().numpy())
+                np.save(os.path.join(d, "icp_idx.npy"), icp.idx.cpu().numpy())
+                np.save(os.path.join(d, "icp_d2.npy"), icp.d2.cpu().numpy())
             if obj:
                 np.save(os.path.join(d, "object_labels.npy"), om.labels.cpu().numpy())
                 np.save(os.path.join(d, "obj_R.npy"), om.R.cpu().numpy())
@@ -375,6 +419,25 @@ def evaluate(args):
             rigid_acc3d_strict=emeans[4],
             rigid_acc3d_relax=emeans[5],
             rigid_outlier=emeans[6],
+        )
+    if ego_icp:
+        imeans = [s / max(n, 1) for s in icp_sums]
+        log.info(
+            f"[test {args.dataset} icp max_dist={icp_kw['max_dist']} thresh={icp_kw['thresh']} "
+            f"iters={icp_kw['iters']}] rot_err={imeans[0]:.4f}deg trans_err={imeans[1]:.4f} "
+            f"match={imeans[2]:.4f} rmse={imeans[3]:.4f} "
+            f"icprigid EPE3D={imeans[4]:.4f} Acc3DS={imeans[5]:.4f} Acc3DR={imeans[6]:.4f} "
+            f"Outlier={imeans[7]:.4f}"
+        )
+        results.update(
+            icp_rot_err_deg=imeans[0],
+            icp_trans_err=imeans[1],
+            icp_match_ratio=imeans[2],
+            icp_rmse=imeans[3],
+            icprigid_epe=imeans[4],
+            icprigid_acc3d_strict=imeans[5],
+            icprigid_acc3d_relax=imeans[6],
+            icprigid_outlier=imeans[7],
         )
     if obj:
         omeans = [s / max(n, 1) for s in obj_sums]

@@ -17,6 +17,8 @@ launch-collapse as the training step, applied to serving.
 
     # flow plus the ego-motion it implies and a static/dynamic split:
     flow, ego = pred.predict_ego_motion(xyz1, xyz2)       # ego.R, ego.t, ...
+    # ... refined by ICP against the full-resolution second scan:
+    flow, ego, icp = pred.predict_ego_motion(xyz1, xyz2, icp=True, target=pc2_full)
 
     # flow plus the moving objects in it, each with its own rigid motion:
     flow, om = pred.predict_object_motion(xyz1, xyz2)     # om.labels, om.R, ...
@@ -95,16 +97,31 @@ class Predictor:
 
     @torch.no_grad()
     def predict_ego_motion(self, xyz1: torch.Tensor, xyz2: torch.Tensor,
-                           thresh: float = 0.05, iters: int = 10):
+                           thresh: float = 0.05, iters: int = 10, icp: bool = False,
+                           icp_kw: Optional[dict] = None, target: Optional[torch.Tensor] = None):
         """(flow (B,N,3), ``ops.EgoMotion``): the usual forward (graph
         replay as in ``__call__``), then the robust rigid fit of the final
         flow -- one fused launch, run eagerly after the replay without
-        draining the stream.  Works for any predictor batch."""
+        draining the stream.  Works for any predictor batch.
+
+        ``icp=True`` returns (flow, ego, ``ops.IcpRefine``): the fitted motion
+        refined by point-to-point ICP of the static points of ``xyz1`` against
+        ``target`` ((B,M,3), e.g. the full-resolution second scan; ``xyz2``
+        when it is None), ``ops.icp_refine(xyz1, target, R0=ego.R, t0=ego.t,
+        src_mask=ego.static, **icp_kw)``.  It reads ego.R / ego.t on the
+        device: still no host synchronisation.  ``icp.d2`` is a per-point
+        geometric residual that needs no ground truth.  Without ``icp`` the
+        return value is the pair it always was."""
         from pvraft_amd import ops
 
         flow = self(xyz1, xyz2)
-        ego = ops.ego_motion(xyz1.to(self.device).float(), flow, thresh=thresh, iters=iters)
-        return flow, ego
+        pc1 = xyz1.to(self.device).float()
+        ego = ops.ego_motion(pc1, flow, thresh=thresh, iters=iters)
+        if not icp:
+            return flow, ego
+        dst = (xyz2 if target is None else target).to(self.device).float()
+        refined = ops.icp_refine(pc1, dst, R0=ego.R, t0=ego.t, src_mask=ego.static, **(icp_kw or {}))
+        return flow, ego, refined
 
     @torch.no_grad()
     def predict_object_motion(self, xyz1: torch.Tensor, xyz2: torch.Tensor, **kw):

@@ -893,3 +893,131 @@ def noise_filter(xyz: Tensor, inv: float, r2: float, min_neighbors: int, k: int,
             far = (count < k) | (md.double() > thr.unsqueeze(1))
         keep = el & (count >= min_neighbors) & ~far
         return keep, count, md, stats, ok
+
+
+# ---------------------------------------------------------------------------
+# Grid nearest-neighbour search and ICP refinement (absent in the reference)
+# ---------------------------------------------------------------------------
+
+ICP_MAX_ITERS = 64
+
+
+def radius_params(op: str, radius, name: str = "radius"):
+    """``inv = fp32(1) / fp32(radius)`` and ``r2 = fp32(radius) * fp32(radius)``
+    (rounded once) as Python floats, the numbers every backend of ``op``
+    computes with (those of ``noise_params``).  Raises ValueError."""
+    try:
+        radius = float(radius)
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"{op}: bad argument: {e}") from None
+    if not (radius > 0 and math.isfinite(radius)):
+        raise ValueError(f"{op} requires a finite {name} > 0, got {radius}")
+    r32 = torch.tensor(radius, dtype=torch.float32)
+    inv = float((torch.ones((), dtype=torch.float32) / r32).item())
+    r2 = float((r32 * r32).item())
+    if not (r32.item() > 0 and inv > 0 and math.isfinite(inv) and r2 > 0 and math.isfinite(r2)):
+        raise ValueError(f"{op}: 1 / {name} and {name}**2 are not positive fp32 numbers for {name} = {radius}")
+    return inv, r2
+
+
+def rigid_map(x: Tensor, R: Optional[Tensor], t: Optional[Tensor]) -> Tensor:
+    """``x' = ((R00*x + R01*y) + R02*z) + t0`` and likewise y', z' in fp32,
+    every operation rounded on its own: x (B,N,3), R (B,3,3), t (B,3).  Without
+    R the points come back as they are."""
+    if R is None:
+        return x
+    R, t = R.float(), t.float()
+    rows = [
+        ((R[:, a, 0, None] * x[..., 0] + R[:, a, 1, None] * x[..., 1]) + R[:, a, 2, None] * x[..., 2])
+        + t[:, a, None]
+        for a in range(3)
+    ]
+    return torch.stack(rows, -1)
+
+
+def nearest_in_radius(query: Tensor, support: Tensor, inv: float, r2: float,
+                      query_mask: Optional[Tensor] = None, support_mask: Optional[Tensor] = None,
+                      R: Optional[Tensor] = None, t: Optional[Tensor] = None):
+    """Torch version of ``ops.nearest_in_radius`` with the prepared numbers of
+    ``radius_params``: both candidate conditions (cells at most one apart on
+    every axis, d2 <= r2) by brute force over chunks of queries, so no more
+    than chunk x M pair tests are in memory at once; the smallest d2, ties to
+    the smallest index.  No host synchronisation.  Returns idx (B,Nq) int32,
+    d2 (B,Nq) fp32, ok (B,) bool."""
+    with torch.no_grad():
+        B, Nq, _ = query.shape
+        M = support.shape[1]
+        dev = query.device
+        inf = float("inf")
+        idx = torch.full((B, Nq), -1, dtype=torch.int32, device=dev)
+        best = torch.full((B, Nq), inf, dtype=torch.float32, device=dev)
+        ok = torch.ones(B, dtype=torch.bool, device=dev)
+        if B == 0 or Nq == 0 or M == 0:
+            return idx, best, ok
+        x = rigid_map(query.float(), R, t)
+        s = support.float()
+        elq, qq = grid_cells(x, inv, query_mask)
+        els, qs = grid_cells(s, inv, support_mask)
+        cq = torch.where(elq.unsqueeze(-1), qq, torch.zeros_like(qq)).to(torch.int32)  # cells, exact
+        cs = torch.where(els.unsqueeze(-1), qs, torch.zeros_like(qs)).to(torch.int32)
+        r2t = torch.tensor(r2, dtype=torch.float32, device=dev)
+        ar = torch.arange(M, device=dev)
+        chunk = max(1, min(Nq, NOISE_PAIR_BUDGET // M))
+        for b in range(B):
+            for lo in range(0, Nq, chunk):
+                hi = min(Nq, lo + chunk)
+                cand = elq[b, lo:hi, None] & els[b, None, :]
+                d2 = None
+                for a in range(3):
+                    cand &= (cq[b, lo:hi, None, a] - cs[b, None, :, a]).abs() <= 1
+                    d = x[b, lo:hi, None, a] - s[b, None, :, a]
+                    d = d * d
+                    d2 = d if d2 is None else d2 + d  # (dx*dx + dy*dy) + dz*dz, each op rounded
+                cand &= d2 <= r2t
+                d2 = torch.where(cand, d2, torch.full_like(d2, inf))
+                m = d2.min(1).values
+                first = torch.where(cand & (d2 == m.unsqueeze(1)), ar, torch.full_like(ar, M)).min(1).values
+                found = first < M
+                idx[b, lo:hi] = torch.where(found, first, torch.full_like(first, -1)).int()
+                best[b, lo:hi] = torch.where(found, m, torch.full_like(m, inf))
+        return idx, best, ok
+
+
+def icp_refine(src: Tensor, dst: Tensor, inv: float, r2: float, th2: float, iters: int,
+               src_mask: Optional[Tensor] = None, dst_mask: Optional[Tensor] = None,
+               R0: Optional[Tensor] = None, t0: Optional[Tensor] = None):
+    """Torch version of ``ops.icp_refine`` with the prepared numbers (``inv``,
+    ``r2`` of max_dist and ``th2 = fp32(thresh)**2`` from ``radius_params``):
+    the loop of its docstring over ``nearest_in_radius`` and ``rigid_fit`` of
+    this module, every cloud's stop carried as a mask so that nothing
+    synchronises with the host.  Returns R (B,3,3), t (B,3), idx (B,N) int32,
+    d2 (B,N), matched (B,) int32, rounds (B,) int32, ok (B,) bool."""
+    with torch.no_grad():
+        B, N, _ = src.shape
+        dev = src.device
+        src, dst = src.float(), dst.float()
+        R = torch.eye(3, device=dev).repeat(B, 1, 1) if R0 is None else R0.float().clone()
+        t = torch.zeros(B, 3, device=dev) if t0 is None else t0.float().clone()
+        stopped = torch.zeros(B, dtype=torch.bool, device=dev)
+        rounds = torch.zeros(B, dtype=torch.int32, device=dev)
+        th2t = torch.tensor(th2, dtype=torch.float32, device=dev)
+        bidx = torch.arange(B, device=dev).unsqueeze(1)
+        search_ok = torch.ones(B, dtype=torch.bool, device=dev)
+        for k in range(int(iters) + 1):
+            idx, d2, sok = nearest_in_radius(src, dst, inv, r2, src_mask, dst_mask, R, t)
+            search_ok &= sok
+            found = idx >= 0
+            if k == iters:
+                break
+            if dst.shape[1] > 0:
+                matched = torch.where(found.unsqueeze(-1), dst[bidx, idx.clamp_min(0).long()], src)
+            else:
+                matched = src
+            w = torch.where(found, 1.0 / (1.0 + d2 / th2t), torch.zeros_like(d2))
+            Rf, tf, _, fok = rigid_fit(src, matched, w, 1.0, 0)
+            go = ~stopped & (found.sum(1) >= 3) & fok
+            R = torch.where(go.view(B, 1, 1), Rf, R)
+            t = torch.where(go.view(B, 1), tf, t)
+            rounds = rounds + go.int()
+            stopped = stopped | ~go
+        return R.contiguous(), t, idx, d2, found.sum(1).int(), rounds, search_ok & ~stopped

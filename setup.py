@@ -42,6 +42,7 @@ SOURCES = [
     "pvraft_amd/csrc/plane_fit.hip",
     "pvraft_amd/csrc/voxel_sample.hip",
     "pvraft_amd/csrc/noise_filter.hip",
+    "pvraft_amd/csrc/grid_nn.hip",
 ]
 
 setup(

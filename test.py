@@ -44,6 +44,10 @@ def parse_args():
     parser.add_argument("--noise_min_neighbors", help="a point with fewer neighbours within the radius is noise", default=4, type=int)
     parser.add_argument("--noise_k", help="nearest neighbours in the mean-distance statistic of the noise filter (0 disables it)", default=8, type=int)
     parser.add_argument("--noise_std_ratio", help="a point whose mean distance exceeds mean + ratio * std is noise", default=2.0, type=float)
+    parser.add_argument("--ego_icp", help="with --ego_motion: refine the fitted motion by ICP of the static points against the full second scan (ops.icp_refine) and report icp_* / icprigid_* metrics", action="store_true")
+    parser.add_argument("--icp_max_dist", help="largest correspondence distance of the ICP refinement (m)", default=1.0, type=float)
+    parser.add_argument("--icp_thresh", help="Cauchy scale of the ICP weights (m)", default=0.1, type=float)
+    parser.add_argument("--icp_iters", help="rounds of the ICP refinement", default=10, type=int)
     return parser.parse_args()
 
 
